@@ -6,11 +6,15 @@ the N ranks runs 16/N micro-steps of fwd+bwd on one synthetic 1536-frame x 8x8 l
 the Muon (libowlk Newton-Schulz) + AdamW step and the EMA update.  Strong scaling: total work per
 step is fixed as N grows.  value = 16 * 98,304 * K tokens / (max-over-ranks wall time of K steps).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
-Extra fields: roofline (dominant kernel, HIP events on the launch stream, algorithmic FLOPs),
-cpu_baseline (the fp32 CPU oracle at dit_v4 width/depth on 1,024 tokens, rank 0 at N=1 only).
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+then also writes what the last timed step computed (dump_outputs).  --full adds the measurements
+that take runs of their own and their fields: roofline (dominant kernel, HIP events on the launch
+stream, algorithmic FLOPs; HBM traffic from two rocprofv3 PMC passes), kernel_rates, cpu_baseline
+(the fp32 CPU oracle at dit_v4 width/depth on 1,024 tokens, rank 0 at N=1 only); --no-profile,
+--no-traffic and --no-cpu-baseline drop single ones of them.
 """
 import argparse
 import json
@@ -233,6 +237,37 @@ def microsteps(args):
     log("[microsteps] done")
 
 
+DUMP_PER_TENSOR = 4096  # sampled elements per parameter tensor: 905,344 values = 3.6 MB per array for dit_v4
+
+
+def dump_outputs(path, losses, model, ema_model):
+    """--dump-outputs: what the last timed step handed back, as float32 DIR/<name>.npy --
+    loss   [accum]  the micro-step losses as the step computed them (each already / accum),
+    params [n]      the model's parameters after the step's Muon / AdamW update,
+    ema    [n]      the EMA model's parameters after its update;
+    params / ema hold, per parameter tensor in parameters() order, the whole tensor if it has at
+    most DUMP_PER_TENSOR elements and else that many elements at seeded positions (the same
+    positions in every run and in both arrays)."""
+    import numpy as np
+
+    def sample(params):
+        g = torch.Generator().manual_seed(20240531)
+        out = []
+        for p in params:
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_PER_TENSOR:
+                flat = flat[torch.randint(flat.numel(), (DUMP_PER_TENSOR,), generator=g).to(flat.device)]
+            out.append(flat.float().cpu())
+        return torch.cat(out).numpy()
+
+    arrays = {"loss": torch.stack([x.float() for x in losses]).cpu().numpy(),
+              "params": sample(model.parameters()), "ema": sample(ema_model.parameters())}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"[bench] wrote {', '.join(f'{n}.npy {a.shape}' for n, a in arrays.items())} to {path}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -245,20 +280,28 @@ def main():
     ap.add_argument("--lean", type=int, default=None, help="override model.lean_activations (0 / 1)")
     ap.add_argument("--ckpt-layers", type=int, default=None,
                     help="checkpoint only the first N blocks (configs with gradient_checkpointing)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's outputs (see dump_outputs) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the PMC traffic passes, the per-kernel profile (roofline, kernel_rates) and the "
+                         "CPU baseline; a plain run only times the steps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true",
+                    help="with --full: skip the per-kernel profile and the PMC traffic passes")
     ap.add_argument("--config", default="configs/dit_v4.yml",
                     help="model config; the headline metric is dit_v4 (others, e.g. dit_v4_5B, report their own line)")
     ap.add_argument("--microsteps", type=int, default=0, help="(internal) run K fwd+bwd micro-steps and exit")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the live PMC traffic passes")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the live PMC traffic passes")
     args = ap.parse_args()
     if args.microsteps:
         return microsteps(args)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(
         os.environ.get("LOCAL_RANK", 0))
     traffic = {}
-    if rank == 0 and world == 1 and not args.no_traffic and not args.no_profile:
+    if args.full and rank == 0 and world == 1 and not args.no_traffic and not args.no_profile:
         traffic = pmc_traffic(args)  # before this process initialises the GPU
     if os.environ.get("OWL_BENCH_SHARE_GPU") == "1":
         # rehearsal of the multi-rank path on a box with fewer GPUs than ranks (tools/rccl_rehearsal.sh)
@@ -324,11 +367,11 @@ def main():
         return loss
 
     def step():
-        for i in range(accum):
-            micro(i, i == accum - 1)
+        losses = [micro(i, i == accum - 1).detach() for i in range(accum)]
         opt.step()
         red.zero_grad()
         ema.update()
+        return losses
 
     for w in range(args.warmup):
         t0 = time.time()
@@ -341,7 +384,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        step()
+        losses = step()
         if rank == 0:
             log(f"[bench] step {s} issued at {time.perf_counter() - t0:.2f}s")
     torch.cuda.synchronize()
@@ -355,10 +398,12 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     total_tokens = args.global_batch * tokens * args.steps
     value = total_tokens / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, model, ema.ema_model)
 
     # ---- roofline of the dominant kernel: one extra micro-step with HIP events around every launch
     roof, kernels = None, None
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         torch.cuda.synchronize()
         _lib.profile_begin()
         micro(0, False)
@@ -399,7 +444,7 @@ def main():
     log(f"[bench] peak HBM allocated {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
         cpu = cpu_baseline()
 
     if rank == 0:

@@ -594,3 +594,32 @@ def test_grad_reducer_stacks_tagged_params_back_to_back():
             assert (ws[0].grad == 1).all() and (ws[1].grad == 0).all()
         for h in red.hooks:
             h.remove()
+
+
+def test_bench_dump_outputs_arrays(tmp_path):
+    """bench.py --dump-outputs: float32 loss / params / ema arrays; small tensors whole, larger ones at
+    the same seeded positions in both arrays and in every call."""
+    import numpy as np
+    from bench import DUMP_PER_TENSOR, dump_outputs
+    torch.manual_seed(3)
+    model = torch.nn.Sequential(torch.nn.Linear(96, 96), torch.nn.Linear(96, 4)).double()
+    ema = torch.nn.Sequential(torch.nn.Linear(96, 96), torch.nn.Linear(96, 4)).double()
+    assert model[0].weight.numel() > DUMP_PER_TENSOR > model[0].bias.numel()
+    losses = [torch.tensor(0.25), torch.tensor(0.5, dtype=torch.bfloat16)]
+    dump_outputs(str(tmp_path / "a"), losses, model, ema)
+    torch.rand(7)  # the positions do not depend on the global generator
+    dump_outputs(str(tmp_path / "b"), losses, model, model)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("loss", "params", "ema")}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("loss", "params", "ema")}
+    assert sorted(os.listdir(tmp_path / "a")) == ["ema.npy", "loss.npy", "params.npy"]
+    assert all(v.dtype == np.float32 for v in a.values())
+    assert a["loss"].tolist() == [0.25, 0.5]
+    n = DUMP_PER_TENSOR + 96 + 4 * 96 + 4
+    assert a["params"].shape == a["ema"].shape == (n,)
+    assert np.array_equal(a["params"], b["params"]) and np.array_equal(b["params"], b["ema"])
+    assert not np.array_equal(a["params"], a["ema"])
+    # whole small tensors in parameters() order after the sampled first weight
+    tail = torch.cat([p.detach().reshape(-1) for p in list(model.parameters())[1:]]).float().numpy()
+    assert np.array_equal(a["params"][DUMP_PER_TENSOR:], tail)
+    w = model[0].weight.detach().reshape(-1).float().numpy()
+    assert np.isin(a["params"][:DUMP_PER_TENSOR], w).all()

@@ -825,6 +825,47 @@ def test_bench_two_ranks_json_line():
     assert abs(d["tokens_per_s_per_gpu"] - d["value"] / d["n_gpus"]) <= 0.1
 
 
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain bench.py run (no --full) on the TINY config: the result line keeps the contract's keys
+    with no profile / CPU-baseline fields filled, --steps sets the timed steps, and --dump-outputs
+    writes the last step's loss / params / ema as float32 .npy files of the documented sizes."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    from bench import DUMP_PER_TENSOR
+    from owl_wms.configs import model_config
+    from owl_wms.models.gamerft import GameRFT
+    _tiny_trainer_cfg(tmp_path)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--global-batch", "2", "--config", str(tmp_path / "c.yml"), "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=str(tmp_path), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert key in d, key
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    assert d["unit"] == "latent-tokens/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    tol = 1e-3 + 0.05 / d["ms_per_step"]  # ms_per_step is rounded to 0.1 ms
+    assert abs(d["value"] - 2 * 8 * 64 / (d["ms_per_step"] / 1e3)) <= tol * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and "kernel_rates" not in d
+    assert r.stderr.count("[bench] step ") == 2 and "PMC pass" not in r.stderr
+    assert sorted(p.name for p in out.iterdir()) == ["ema.npy", "loss.npy", "params.npy"]
+    n = sum(min(p.numel(), DUMP_PER_TENSOR) for p in GameRFT(model_config(**TINY)).parameters())
+    arrays = {k: np.load(out / f"{k}.npy") for k in ("loss", "params", "ema")}
+    assert arrays["loss"].shape == (2,) and arrays["params"].shape == arrays["ema"].shape == (n,)
+    for a in arrays.values():
+        assert a.dtype == np.float32 and np.isfinite(a).all()
+    assert (arrays["loss"] > 0).all() and arrays["params"].std() > 0
+    # the EMA copies the weights on its first updates (decay 0 at step 0 and 1), then lags them
+    assert not np.array_equal(arrays["params"], arrays["ema"])
+    assert np.abs(arrays["params"] - arrays["ema"]).max() < 0.1
+
+
 def test_trainer_eval_sampler_at_sample_interval(tmp_path):
     """rft_trainer.py:213, 243-280: the EMA model's sampler runs at step 0 and every
     sample_interval; latents land in eval_sample_dir as vid.<step>.pt (4 context + 2 generated)."""
