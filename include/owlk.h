@@ -213,6 +213,25 @@ int owlk_attn_bwd_dq(const void* q, long ldq, long sqb, const void* k, long ldk,
                      float scale, long tpf, int window, int causal, const int* kv_lo, const int* q_hi,
                      const int* run_start, const int* doc, long fstride, void* stream);
 
+/* Backward of the unmasked KV-cache decode attention: the gradient autograd runs for the cache branch
+ * of attn.py:86-107 when a self-forcing rollout backpropagates through one decode step
+ * (sf_vid_only.py:181-188).  q, dout, dq [B, Lq, H D]; k, v [B, Lkv, H D] = [cache | the Lnew new
+ * rows] (the already-windowed view for a local layer, as the forward takes it); lse (base 2, as
+ * owlk_attn_fwd writes it) and delta (owlk_attn_delta) [B, H, Lq] fp32.  dq = scale dS K over all
+ * Lkv keys; dk_new, dv_new [B, Lnew, H D] = scale dS^T Q and P^T dO of the LAST Lnew key rows only (the
+ * cache is a constant: nothing is formed or written for its rows; both may be null when Lnew = 0).
+ * Any Lq >= 1 and Lkv >= Lnew >= 0, head_dim 64 or 128; token-major strided views (row strides
+ * multiples of 8 below 2^31, pointers 16-byte aligned).  The keys are split over workgroups by a
+ * rule of Lkv and head_dim alone; each split's fp32 partial dQ goes to ws (caller-owned, >=
+ * owlk_attn_decode_bwd_ws_bytes, 256-byte aligned) and a second launch adds them in split order: no
+ * float atomics, no waiting between workgroups, bitwise reproducible on every device. */
+long owlk_attn_decode_bwd_ws_bytes(long B, int H, long Lq, long Lkv, int head_dim);
+int owlk_attn_decode_bwd(const void* q, long ldq, long sqb, const void* k, long ldk, long skb, const void* v,
+                         long ldv, long svb, const void* dout, long ldo, long sob, const float* lse,
+                         const float* delta, void* dq, long lddq, long sdqb, void* dk_new, long lddk, long sdkb,
+                         void* dv_new, long lddv, long sdvb, long B, int H, long Lq, long Lkv, long Lnew,
+                         int head_dim, float scale, void* ws, long ws_bytes, void* stream);
+
 /* Single-pass backward (head_dim 64, Lq == Lkv == L; frame masks windowed or not, and causal masks of packed
  * documents given as kv_lo / q_hi alone, every document one run of frames -- run_start / doc must be
  * null, as owlk_attn_bwd's runs form): the same

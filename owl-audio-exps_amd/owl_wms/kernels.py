@@ -586,6 +586,55 @@ def attn_bwd(q, k, v, o, do, lse, H, D, mask, dq, dk, dv, scale=None, delta=None
          flops=lambda: 2.0 * D * H * B * mask_pairs(mask, L, L))
 
 
+_DECODE_BWD_WS = {}
+
+
+def _decode_bwd_ws(device, nbytes):
+    """attn_decode_bwd's workspace (the key splits' fp32 partial dQ): one buffer per device, reused
+    by every call and grown by reallocation.  Each call writes every partial it later reads, so the
+    buffer carries no state between calls; calls on one device must be on one stream (autograd
+    runs a rollout's backward on one)."""
+    key = torch.device(device)
+    buf = _DECODE_BWD_WS.get(key)
+    if buf is None or buf.numel() < nbytes:
+        _DECODE_BWD_WS[key] = buf = torch.empty(max(nbytes, 1 << 20), device=device, dtype=torch.uint8)
+    return buf
+
+
+def attn_decode_bwd(q, k, v, o, do, lse, H, D, Lnew, dq, dk_new, dv_new, scale=None, delta=None):
+    """Backward of the unmasked decode attention (attn_fwd with FrameMask(1, None, False, 0, None)): q, o,
+    do, dq [B, Lq, cols]; k, v [B, Lkv, cols] = [cache | the Lnew new rows]; dk_new, dv_new [B, Lnew,
+    cols] receive the gradients of the last Lnew key rows only (None with Lnew = 0): the cache is a
+    constant.  Same conventions as attn_bwd; delta as there."""
+    for t, n in ((q, "q"), (k, "k"), (v, "v"), (o, "o"), (do, "do"), (dq, "dq")):
+        _v3(t, n)
+    B, Lq, Lkv = q.shape[0], q.shape[1], k.shape[1]
+    Lnew = int(Lnew)
+    assert k.shape[0] == B and v.shape[:2] == k.shape[:2] and do.shape[:2] == q.shape[:2] == dq.shape[:2]
+    assert 0 <= Lnew <= Lkv and lse.shape == (B, H, Lq) and lse.dtype == F32 and lse.is_contiguous()
+    if Lnew:
+        _v3(dk_new, "dk_new"), _v3(dv_new, "dv_new")
+        assert dk_new.shape[:2] == (B, Lnew) and dv_new.shape[:2] == (B, Lnew)
+    else:
+        dk_new = dv_new = None
+    scale = D ** -0.5 if scale is None else scale
+    if delta is None:
+        delta = torch.empty(B, H, Lq, device=q.device, dtype=F32)
+        assert o.is_contiguous() and do.is_contiguous() and o.shape == do.shape
+        call("owlk_attn_delta", ptr(o), ptr(do), o.stride(1), B, Lq, H, D, ptr(delta), stream())
+    else:
+        assert delta.shape == (B, H, Lq) and delta.dtype == F32 and delta.is_contiguous()
+    nb = lib().owlk_attn_decode_bwd_ws_bytes(B, H, Lq, Lkv, D)
+    ws = _decode_bwd_ws(q.device, nb)
+    st = lambda t: (0, 0) if t is None else (t.stride(1), t.stride(0))  # noqa: E731
+    # algorithmic FLOPs: dQ and dP over every key, plus the new rows' share (SURVEY §8(d) counts 8 D per pair)
+    call("owlk_attn_decode_bwd", ptr(q), q.stride(1), q.stride(0), ptr(k), k.stride(1), k.stride(0),
+         ptr(v), v.stride(1), v.stride(0), ptr(do), do.stride(1), do.stride(0), ptr(lse), ptr(delta),
+         ptr(dq), dq.stride(1), dq.stride(0), ptr(dk_new), *st(dk_new), ptr(dv_new), *st(dv_new),
+         B, H, Lq, Lkv, Lnew, D, float(scale), ptr(ws), ws.numel(), stream(),
+         key="attn_decode_bwd", flops=8.0 * D * H * B * Lq * Lkv)
+
+
 def mask_pairs(mask, Lq, Lkv):
     """Allowed (query, key) pairs per (batch, head), averaged over the batch (SURVEY §8(d) counts
     algorithmic FLOPs over allowed pairs only).  With document arrays the doc predicate is counted

@@ -50,6 +50,10 @@ class GameRFTCore(nn.Module):
         x_tok = x.permute(0, 1, 3, 4, 2).reshape(b, n * h * w, c)
         y = self.forward_tokens(x_tok, t, mouse, btn, doc_id, has_controls, kv_cache, local_block_mask,
                                 global_block_mask)
+        if torch.is_grad_enabled() and y.requires_grad:
+            # the same rearrangement through autograd ('b (n h w) c -> b n c h w'): the velocity of a
+            # decode step inside a self-forcing rollout carries its gradient to the caller
+            return y.view(b, n, h, w, c).permute(0, 1, 4, 2, 3).contiguous()
         return K.unpatchify(y.reshape(-1, c).contiguous(), b, n, c, h, w)
 
 

@@ -8,6 +8,9 @@ Training path: ``DiTBlock.forward`` -> ``DiTBlockFn`` (whole block fwd+bwd fused
 Sampling path (``kv_cache`` given): a no-grad functional path with the reference's cache
 semantics (attn.py:86-107): cached K/V prepended, local layers keep the last
 ``local_window * tokens_per_frame`` keys when decoding unmasked.
+Decode step with a gradient (``decode_carries_grad``: an unmasked decode against a constant cache,
+autograd on, something requiring grad -- the last Euler step of a self-forcing rollout frame):
+``DiTBlockFn`` with a decode geometry, the same forward bit for bit, the cache a constant.
 """
 import torch
 import weakref
@@ -73,6 +76,19 @@ def check_rope_rows(rope, offset, n):
     if offset < 0 or offset + n > rows:
         raise RuntimeError(f"RoPE positions {offset}..{offset + n - 1} lie past the {rows}-row table "
                            f"(config.n_frames frames); decode at most n_frames frames of context + new frames")
+
+
+def decode_carries_grad(kv_cache, block_mask, inputs, module):
+    """True when a KV-cache forward must be differentiable: an unmasked decode step (block_mask None)
+    that reads a constant cache (no cache update, no device-resident cache state) with autograd on and
+    an input or a parameter of `module` requiring grad.  Every other cached forward -- the samplers',
+    cache-updating and masked ones -- runs the no-grad path."""
+    if kv_cache is None or block_mask is not None or not torch.is_grad_enabled():
+        return False
+    if kv_cache.should_update or getattr(kv_cache, "dev", None) is not None:
+        return False
+    return any(t is not None and t.requires_grad for t in inputs) or \
+        any(p.requires_grad for p in module.parameters())
 
 
 class Attn(nn.Module):
@@ -179,7 +195,9 @@ class DiTBlock(nn.Module):
 
     def forward(self, x, cond, block_mask, kv_cache=None, mods=None, scond=None):
         """scond: silu(cond) from fused.cond_silu / cond.CondFn (computed here when not given)."""
-        if kv_cache is not None:
+        decode_grad = kv_cache is not None and mods is None and \
+            decode_carries_grad(kv_cache, block_mask, (x, scond if scond is not None else cond), self)
+        if kv_cache is not None and not decode_grad:
             with torch.no_grad():
                 return self._forward_cached(x, cond, block_mask, kv_cache, mods, scond)
         cfg = self.config
@@ -190,11 +208,21 @@ class DiTBlock(nn.Module):
         W, bvec = stacked_modulation_weights(self, mparams)
         H = cfg.n_heads
         rope = self.attn.rope
-        ck = getattr(self, "_checkpointed", False)
-        geo = BlockGeometry(H, cfg.d_model // H, cfg.tokens_per_frame, block_mask, rope.cos, rope.sin, 0,
-                            keep_attn=id(self) if ck else None,
-                            lean=bool(getattr(cfg, "lean_activations", False)) and not ck)
         a, m = self.attn, self.mlp
+        if decode_grad:
+            # a decode step that carries a gradient (the last Euler step of a self-forcing rollout frame):
+            # _forward_cached's computation as the fused block, RoPE at the layer's cache offset, the
+            # cache a constant (the block keeps its own copy of the keys it attends to, fused._decode_keys)
+            offset = kv_cache.get_offset(a.layer_idx)
+            check_rope_rows(rope, offset, x.shape[1])
+            ck_, cv_ = kv_cache.get(a.layer_idx) if offset > 0 else (None, None)
+            geo = BlockGeometry(H, cfg.d_model // H, cfg.tokens_per_frame, None, rope.cos, rope.sin, offset,
+                                decode=(ck_, cv_, a.local_offset if a.local else 0))
+        else:
+            ck = getattr(self, "_checkpointed", False)
+            geo = BlockGeometry(H, cfg.d_model // H, cfg.tokens_per_frame, block_mask, rope.cos, rope.sin, 0,
+                                keep_attn=id(self) if ck else None,
+                                lean=bool(getattr(cfg, "lean_activations", False)) and not ck)
         return DiTBlockFn.apply(x.to(torch.bfloat16).contiguous(), scond, W, bvec, geo, a.qkv.weight, a.qkv.bias,
                                 a.out.weight, a.out.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
                                 *mparams)
@@ -265,7 +293,11 @@ class DiT(nn.Module):
         n_ck = getattr(self.config, "checkpoint_layers", None)
         if scond is None:
             scond = cond_silu(cond)
-        mods = self._decode_modulation(scond) if kv_cache is not None else None
+        # a decode step that carries a gradient: each block forms its own modulation inside its autograd
+        # function (fused.DiTBlockFn) instead of reading a slice of the no-grad stacked GEMM
+        masks = local_block_mask if local_block_mask is not None else global_block_mask
+        decode_grad = decode_carries_grad(kv_cache, masks, (x, scond), self)
+        mods = self._decode_modulation(scond) if kv_cache is not None and not decode_grad else None
         d6 = 6 * self.config.d_model
         for i, block in enumerate(self.blocks):
             mask = local_block_mask if self.local_layers[i] else global_block_mask

@@ -296,13 +296,36 @@ def adaln_mod(x, s, w, b, tpf, act=False):
 
 class BlockGeometry:
     """Static per-forward data of a DiT block: heads, frame mask, RoPE tables; keep_attn = a key
-    per block when the block runs under activation checkpointing (see _ATTN_KEEP)."""
+    per block when the block runs under activation checkpointing (see _ATTN_KEEP).
 
-    def __init__(self, n_heads, head_dim, tpf, mask, cos, sin, tab_off=0, keep_attn=None, lean=False):
+    decode = (cache_k, cache_v, window_tokens) makes the block a KV-cache decode step that carries a
+    gradient (attn.py:86-107's cache branch inside a self-forcing rollout, sf_vid_only.py:181-188):
+    RoPE at tab_off = the layer's cache offset, unmasked attention over [cache | new] (its last
+    window_tokens keys on a local layer; 0 = all), the cache a constant.  cache_k / cache_v are the
+    layer's cached [B, n, d] views, or None without a cache; mask is unused."""
+
+    def __init__(self, n_heads, head_dim, tpf, mask, cos, sin, tab_off=0, keep_attn=None, lean=False, decode=None):
         self.H, self.D, self.tpf, self.mask = n_heads, head_dim, tpf, mask
         self.cos, self.sin, self.tab_off = cos, sin, tab_off
         self.keep_attn = keep_attn
         self.lean = lean
+        self.decode = decode
+
+
+_DECODE_MASK = K.FrameMask(1, None, False, 0, None)  # unmasked: every query sees every key
+
+
+def _decode_keys(geo, k_new, v_new):
+    """[cache | new] K and V of a decode block as tensors of the block's OWN: the rollout overwrites
+    the new frame's cache slots, truncates and appends further frames before backward() runs, so the
+    backward must not read the cache buffers in place.  torch.cat copies the cached rows; without a
+    cache the new rows (views of the block's saved qkr / qkv) are the keys."""
+    ck, cv, win = geo.decode
+    if ck is not None and ck.shape[1]:
+        k_new, v_new = torch.cat([ck, k_new], dim=1), torch.cat([cv, v_new], dim=1)
+    if win:
+        k_new, v_new = k_new[:, -win:], v_new[:, -win:]
+    return k_new, v_new
 
 
 # A checkpointed block (dit_v4_5B: gradient_checkpointing, attn.py:186) runs its forward again
@@ -347,7 +370,11 @@ class DiTBlockFn(torch.autograd.Function):
         qkv, qkr, rq = K.gemm_qk_rope(h1, bf16_weight(wqkv), bqkv, H, D, geo.cos, geo.sin, geo.tab_off, T)
         q3, k3 = qkr.view(B, T, 2 * d)[:, :, :d], qkr.view(B, T, 2 * d)[:, :, d:]
         kept = _kept_attention(geo, x, wqkv)
-        if kept is not None:
+        kd = vd = None
+        if geo.decode is not None:
+            kd, vd = _decode_keys(geo, k3, qkv.view(B, T, 3 * d)[:, :, 2 * d:])
+            o, lse = K.attn_fwd(q3, kd, vd, H, D, _DECODE_MASK, score_bound=K.qk_norm_bound(D))
+        elif kept is not None:
             o, lse = kept
         else:
             o, lse = K.attn_fwd(q3, k3, qkv.view(B, T, 3 * d)[:, :, 2 * d:], H, D, geo.mask,
@@ -369,7 +396,7 @@ class DiTBlockFn(torch.autograd.Function):
             # bf16 units per block
             h1 = qkr = h2 = a = x1 = None
         ctx.save_for_backward(xx, s2, wmod, mods, wqkv, wout, w1, w2, h1, r1, qkv, qkr, rq, o, lse, y1, x1, h2,
-                              r2, a_pre, a, y2)
+                              r2, a_pre, a, y2, kd, vd)
         ctx.geo, ctx.shape, ctx.sshape = geo, (B, T, d), s.shape
         ctx.params = (wqkv, bqkv, wout, bout, w1, b1, w2, b2) + tuple(mparams)
         ctx.cg = cond_grad_of(s)
@@ -378,7 +405,7 @@ class DiTBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         (xx, s2, wmod, mods, wqkv, wout, w1, w2, h1, r1, qkv, qkr, rq, o, lse, y1, x1, h2, r2, a_pre, a,
-         y2) = ctx.saved_tensors
+         y2, kd, vd) = ctx.saved_tensors
         geo = ctx.geo
         B, T, d = ctx.shape
         M = B * T
@@ -433,8 +460,19 @@ class DiTBlockFn(torch.autograd.Function):
         dqkr = torch.empty(M, 2 * d, device=xx.device, dtype=BF16)
         q3, k3 = qkr.view(B, T, 2 * d)[:, :, :d], qkr.view(B, T, 2 * d)[:, :, d:]
         dq3, dk3 = dqkr.view(B, T, 2 * d)[:, :, :d], dqkr.view(B, T, 2 * d)[:, :, d:]
-        K.attn_bwd(q3, k3, qkv.view(B, T, 3 * d)[:, :, 2 * d:], o.view(B, T, d), do.view(B, T, d), lse, H, D,
-                   geo.mask, dq3, dk3, dqkv.view(B, T, 3 * d)[:, :, 2 * d:], delta=delta)
+        dv3 = dqkv.view(B, T, 3 * d)[:, :, 2 * d:]
+        if geo.decode is not None:
+            # gradients of the new rows only (the last n_new keys); a window shorter than the new rows
+            # leaves the first of them unseen: zero gradient
+            n_new = min(T, kd.shape[1])
+            if n_new < T:
+                dk3[:, :T - n_new].zero_()
+                dv3[:, :T - n_new].zero_()
+            K.attn_decode_bwd(q3, kd, vd, o.view(B, T, d), do.view(B, T, d), lse, H, D, n_new, dq3,
+                              dk3[:, T - n_new:], dv3[:, T - n_new:], delta=delta)
+        else:
+            K.attn_bwd(q3, k3, qkv.view(B, T, 3 * d)[:, :, 2 * d:], o.view(B, T, d), do.view(B, T, d), lse, H, D,
+                       geo.mask, dq3, dk3, dv3, delta=delta)
         del do, delta
         # qkv bias gradient: the q / k columns' sums fused into the rope backward, the v columns' by colsum
         sink_bqkv = grad_sink(prm[1])

@@ -11,5 +11,8 @@ def get_trainer_cls(trainer_id):
     if trainer_id == "av":
         from .rft_trainer import AVRFTTrainer
         return AVRFTTrainer
-    raise NotImplementedError(f"trainer {trainer_id!r} is out of scope for the MI355X hot-path build "
-                              "(distillation / self-forcing trainers, SURVEY.md §2.1)")
+    raise NotImplementedError(f"trainer {trainer_id!r}: the distillation trainer classes are not built (SURVEY.md "
+                              "§2.1).  Their core is: trainers/self_forcing.py has the self-forcing rollout "
+                              "(RolloutManager, gradients through the KV-cache decode step) and the critic / DMD "
+                              "losses; the trainer class around them (teacher checkpoint, VAE decoder, EMA, "
+                              "logging) is not")
