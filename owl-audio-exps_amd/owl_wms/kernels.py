@@ -222,11 +222,6 @@ def adaln_bwd_into(dy, x, rstd, scale, tpf, dmod, dres=None, ypre=None):
     return dx
 
 
-# the DiT / MMDiT blocks' MLP-branch AdaLN backward with the attention gate's backward in one pass
-# (owlk_adaln_gate_bwd); OWLK_ADALN_GATE=0 runs the two passes (same bits), for A/B runs
-ADALN_GATE = os.environ.get("OWLK_ADALN_GATE", "1") != "0"
-
-
 def adaln_gate_bwd_into(dy, x, rstd, scale, tpf, dmod, dres, y, g, dg_out, want_bias=True):
     """adaln_bwd_into followed by gate_bwd on its dx, in one pass (dx is not read back): ->
     dx [T, d] bf16, the gate backward's dy [T, d] bf16, per-frame bias partials [F, d] fp32 (or None);

@@ -18,7 +18,7 @@ from torch import nn
 from torch.utils.checkpoint import checkpoint as torch_checkpoint
 
 from .. import kernels as K
-from .fused import (BlockGeometry, DiTBlockFn, ModFn, adaln_mod, bf16_weight, cond_silu, linear,
+from .fused import (BlockGeometry, DiTBlockFn, ModFn, adaln_mod, bf16_weight, block_tail, cond_silu, linear,
                     stacked_modulation_weights)
 from .mlp import MLP
 from .modulation import AdaLN, Gate
@@ -193,6 +193,11 @@ class DiTBlock(nn.Module):
         fcs = (self.adaln1.fc, self.gate1.fc_c, self.adaln2.fc, self.gate2.fc_c)
         return [f.weight for f in fcs], [f.bias for f in fcs]
 
+    def tail_params(self):
+        """(wout, bout, w1, b1, w2, b2): the block's parameters after the attention (fused.block_tail)"""
+        a, m = self.attn, self.mlp
+        return a.out.weight, a.out.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias
+
     def forward(self, x, cond, block_mask, kv_cache=None, mods=None, scond=None):
         """scond: silu(cond) from fused.cond_silu / cond.CondFn (computed here when not given)."""
         decode_grad = kv_cache is not None and mods is None and \
@@ -208,7 +213,7 @@ class DiTBlock(nn.Module):
         W, bvec = stacked_modulation_weights(self, mparams)
         H = cfg.n_heads
         rope = self.attn.rope
-        a, m = self.attn, self.mlp
+        a = self.attn
         if decode_grad:
             # a decode step that carries a gradient (the last Euler step of a self-forcing rollout frame):
             # _forward_cached's computation as the fused block, RoPE at the layer's cache offset, the
@@ -224,8 +229,7 @@ class DiTBlock(nn.Module):
                                 keep_attn=id(self) if ck else None,
                                 lean=bool(getattr(cfg, "lean_activations", False)) and not ck)
         return DiTBlockFn.apply(x.to(torch.bfloat16).contiguous(), scond, W, bvec, geo, a.qkv.weight, a.qkv.bias,
-                                a.out.weight, a.out.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias,
-                                *mparams)
+                                *self.tail_params(), *mparams)
 
     def _forward_cached(self, x, cond, block_mask, kv_cache, mods=None, scond=None):
         """No-grad forward of the decode path (attn.py:86-107 cache branch).  mods: this block's
@@ -238,19 +242,11 @@ class DiTBlock(nn.Module):
             W, bvec = stacked_modulation_weights(self, [t for pair in zip(ws, bs) for t in pair])
             s = scond if scond is not None else cond_silu(cond)
             mods = K.gemm(s.reshape(-1, d).to(torch.bfloat16).contiguous(), W, bias=bvec)
-        ab1, g1, ab2, g2 = mods[:, :2 * d], mods[:, 2 * d:3 * d], mods[:, 3 * d:5 * d], mods[:, 5 * d:]
         xx = x.reshape(B * L, d).to(torch.bfloat16).contiguous()
-        ab1, ab2 = ab1.reshape(-1, 2 * d), ab2.reshape(-1, 2 * d)
-        h1, _ = K.adaln_fwd(xx, ab1[:, :d], ab1[:, d:], tpf)
+        h1, _ = K.adaln_fwd(xx, mods[:, :d], mods[:, d:2 * d], tpf)
         qkv = K.gemm(h1, bf16_weight(self.attn.qkv.weight), bias=self.attn.qkv.bias)
         o = self.attn._attend(qkv, B, L, block_mask, kv_cache)
-        x1 = K.gemm(o.reshape(B * L, d), bf16_weight(self.attn.out.weight), bias=self.attn.out.bias,
-                    epi=K.EPI_GATE_RESID, gate=g1.reshape(-1, d), tpf=tpf, resid=xx)
-        h2, _ = K.adaln_fwd(x1, ab2[:, :d], ab2[:, d:], tpf)
-        a_pre = torch.empty(B * L, 4 * d, device=x.device, dtype=torch.bfloat16)
-        a = K.gemm(h2, bf16_weight(self.mlp.fc1.weight), bias=self.mlp.fc1.bias, epi=K.EPI_SILU, aux=a_pre)
-        out = K.gemm(a, bf16_weight(self.mlp.fc2.weight), bias=self.mlp.fc2.bias, epi=K.EPI_GATE_RESID,
-                     gate=g2.reshape(-1, d), tpf=tpf, resid=x1)
+        out, _ = block_tail(o.reshape(B * L, d), xx, mods, tpf, self.tail_params(), save=False)
         return out.view(B, L, d)
 
 

@@ -27,7 +27,6 @@ reducer is told the gradient is complete.  That replaces autograd's separate fp3
 ``p.grad += g`` pass per parameter per micro-step.  It needs each parameter used once per
 forward, which holds for every module on this path.
 """
-import os
 import weakref
 
 import torch
@@ -70,23 +69,26 @@ def grad_done(p):
         r.grad_ready(p)
 
 
-def wgrad_into(p, dy, x):
-    """weight gradient dW = dy^T x: accumulated into p's bucket view (returns None) or returned."""
+def wgrad_into(p, dy, x, done=grad_done):
+    """weight gradient dW = dy^T x: accumulated into p's bucket view (returns None) or returned.
+    done(p) is called once the write into the view is enqueued: grad_done, or a caller's collector
+    where the write is on a side stream the caller has yet to join (mmattn.MMDiTBlockFn)."""
     sink = grad_sink(p)
     if sink is None:
         return K.gemm_wgrad(dy, x)
     K.gemm(dy, x, a_trans=True, b_trans=True, out=sink, out_f32=True, beta=1.0)
-    grad_done(p)
+    done(p)
     return None
 
 
-def bgrad_into(p, dy):
-    """bias gradient sum_rows dy (bf16 or fp32 rows), accumulated into p's bucket view or returned."""
+def bgrad_into(p, dy, done=grad_done):
+    """bias gradient sum_rows dy (bf16 or fp32 rows), accumulated into p's bucket view or returned;
+    done as in wgrad_into."""
     sink = grad_sink(p)
     if sink is None:
         return K.colsum(dy)
     K.colsum(dy, out=sink)
-    grad_done(p)
+    done(p)
     return None
 
 
@@ -349,6 +351,82 @@ def _keep_attention(geo, x, wqkv, o, lse):
         _ATTN_KEEP[geo.keep_attn] = (weakref.ref(x), x._version, wqkv, wqkv._version, o, lse)
 
 
+# The residual branches of a DiT / MMDiT block after its attention, shared by DiTBlockFn, MMDiTBlockFn
+# (once per modality) and the two no-grad cached forwards.  mods is the [F, 6d] modulation matrix,
+# columns [scale1 | shift1 | gate1 | scale2 | shift2 | gate2], one row per frame of tpf rows; tail is
+# (wout, bout, w1, b1, w2, b2), the Parameters themselves (bf16 copies cached, gradient sinks).
+
+
+def block_tail(o, resid, mods, tpf, tail, save=True):
+    """x1 = resid + g1 (o Wout^T + bout); out = x1 + g2 MLP(AdaLN2(x1)) in four launches -> out and
+    (y1, x1, h2, r2, a_pre, a, y2) for block_tail_bwd.  save=False (no-grad forwards): the gated
+    branch outputs y1 / y2 are not written."""
+    wout, bout, w1, b1, w2, b2 = tail
+    M, d = resid.shape
+    y1 = torch.empty(M, d, device=resid.device, dtype=BF16) if save else None
+    x1 = K.gemm(o, bf16_weight(wout), bias=bout, epi=K.EPI_GATE_RESID, aux=y1, gate=mods[:, 2 * d:3 * d], tpf=tpf,
+                resid=resid)
+    h2, r2 = K.adaln_fwd(x1, mods[:, 3 * d:4 * d], mods[:, 4 * d:5 * d], tpf)
+    a_pre = torch.empty(M, w1.shape[0], device=resid.device, dtype=BF16)
+    a = K.gemm(h2, bf16_weight(w1), bias=b1, epi=K.EPI_SILU, aux=a_pre)
+    y2 = torch.empty(M, d, device=resid.device, dtype=BF16) if save else None
+    out = K.gemm(a, bf16_weight(w2), bias=b2, epi=K.EPI_GATE_RESID, aux=y2, gate=mods[:, 5 * d:], tpf=tpf, resid=x1)
+    return out, (y1, x1, h2, r2, a_pre, a, y2)
+
+
+def block_tail_bwd(dout, resid, mods, dm, tpf, tail, saved, done=grad_done):
+    """Backward of block_tail from dout [M, d] to the out-projection's output: -> dx1 (the gradient
+    of x1, dout included), dy1 (of o Wout^T + bout) and (dbout, dw1, db1, dw2, db2), each None where
+    it went into the parameter's bucket view (done: see wgrad_into).  d mods lands in columns
+    [2d, 6d) of dm.  dWout is the caller's: it has o.  Lean activations are the saved tensors that
+    are None: x1 (gate_resid of resid), h2 (adaln_fwd of x1) and a (emitted by the dSiLU epilogue)."""
+    wout, bout, w1, b1, w2, b2 = tail
+    y1, x1, h2, r2, a_pre, a, y2 = saved
+    d = y1.shape[1]
+    g1, sc2, sh2, g2 = mods[:, 2 * d:3 * d], mods[:, 3 * d:4 * d], mods[:, 4 * d:5 * d], mods[:, 5 * d:]
+    if x1 is None:
+        x1 = K.gate_resid(resid, y1, g1, tpf)
+    dy2, _, dbf2 = K.gate_bwd(dout, y2, g2, tpf, dg_out=dm[:, 5 * d:])
+    db2 = bgrad_into(b2, dbf2, done)  # per-frame partials [F, d] -> bias gradient
+    sink_b1 = grad_sink(b1)
+    db1 = sink_b1 if sink_b1 is not None else torch.zeros(a_pre.shape[1], device=a_pre.device, dtype=torch.float32)
+    a_out = None
+    if a is None:
+        a = a_out = torch.empty_like(a_pre)
+    # dSiLU epilogue + column sums (the fc1 bias gradient) (+ a = silu(a_pre) into a_out)
+    dapre = K.gemm(dy2, bf16_weight(w2), b_trans=True, epi=K.EPI_DSILU, aux=a_pre, colsum=db1, resid=a_out)
+    if sink_b1 is not None:
+        done(b1)
+        db1 = None
+    dw2 = wgrad_into(w2, dy2, a, done)
+    del a, a_out, dy2
+    if h2 is None:
+        h2, _ = K.adaln_fwd(x1, sc2, sh2, tpf)
+    dw1 = wgrad_into(w1, dapre, h2, done)
+    del h2
+    dh2 = K.gemm(dapre, bf16_weight(w1), b_trans=True)
+    del dapre
+    # AdaLN2 backward with the attention branch's gate backward fused onto its dx rows
+    dx1, dy1, dbf1 = K.adaln_gate_bwd_into(dh2, x1, r2, sc2, tpf, dm[:, 3 * d:5 * d], dout, y1, g1, dm[:, 2 * d:3 * d])
+    del dh2, x1
+    dbout = bgrad_into(bout, dbf1, done)
+    return dx1, dy1, (dbout, dw1, db1, dw2, db2)
+
+
+def block_head_bwd(dqkv, h1, x, r1, mods, dm, tpf, wqkv, dx1, done=grad_done):
+    """Backward of qkv = AdaLN1(x) Wqkv^T + bqkv given dqkv: -> dx (dx1, the residual's gradient,
+    added) and dWqkv (None when sunk); d [scale1 | shift1] lands in columns [0, 2d) of dm.  The bias
+    gradient is the caller's.  h1 None (lean): recomputed from x."""
+    d = x.shape[1]
+    if h1 is None:
+        h1, _ = K.adaln_fwd(x, mods[:, :d], mods[:, d:2 * d], tpf)
+    dwqkv = wgrad_into(wqkv, dqkv, h1, done)
+    del h1
+    dh1 = K.gemm(dqkv, bf16_weight(wqkv), b_trans=True)
+    dx = K.adaln_bwd_into(dh1, x, r1, mods[:, :d], tpf, dm[:, :2 * d], dres=dx1)
+    return dx, dwqkv
+
+
 class DiTBlockFn(torch.autograd.Function):
     """One DiTBlock with its modulation: mods = s Wmod^T + bmod ([F, 6d], s = silu(cond), the four
     modulation fc's stacked, see stacked_modulation_weights) as the block's first GEMM; the
@@ -363,9 +441,8 @@ class DiTBlockFn(torch.autograd.Function):
         xx = x.reshape(M, d)
         s2 = s.reshape(-1, d).to(BF16).contiguous()
         mods = K.gemm(s2, wmod, bias=bmod)
-        a1, gg1, a2, gg2 = mods[:, :2 * d], mods[:, 2 * d:3 * d], mods[:, 3 * d:5 * d], mods[:, 5 * d:]
 
-        h1, r1 = K.adaln_fwd(xx, a1[:, :d], a1[:, d:], tpf)
+        h1, r1 = K.adaln_fwd(xx, mods[:, :d], mods[:, d:2 * d], tpf)
         # qkv and its QK-RMSNorm + RoPE rows in one launch (the GEMM epilogue)
         qkv, qkr, rq = K.gemm_qk_rope(h1, bf16_weight(wqkv), bqkv, H, D, geo.cos, geo.sin, geo.tab_off, T)
         q3, k3 = qkr.view(B, T, 2 * d)[:, :, :d], qkr.view(B, T, 2 * d)[:, :, d:]
@@ -381,13 +458,7 @@ class DiTBlockFn(torch.autograd.Function):
                                 score_bound=K.qk_norm_bound(D))
             _keep_attention(geo, x, wqkv, o, lse)
         o = o.view(M, d)
-        y1 = torch.empty(M, d, device=x.device, dtype=BF16)
-        x1 = K.gemm(o, bf16_weight(wout), bias=bout, epi=K.EPI_GATE_RESID, aux=y1, gate=gg1, tpf=tpf, resid=xx)
-        h2, r2 = K.adaln_fwd(x1, a2[:, :d], a2[:, d:], tpf)
-        a_pre = torch.empty(M, w1.shape[0], device=x.device, dtype=BF16)
-        a = K.gemm(h2, bf16_weight(w1), bias=b1, epi=K.EPI_SILU, aux=a_pre)
-        y2 = torch.empty(M, d, device=x.device, dtype=BF16)
-        out = K.gemm(a, bf16_weight(w2), bias=b2, epi=K.EPI_GATE_RESID, aux=y2, gate=gg2, tpf=tpf, resid=x1)
+        out, (y1, x1, h2, r2, a_pre, a, y2) = block_tail(o, xx, mods, tpf, (wout, bout, w1, b1, w2, b2))
 
         if geo.lean:
             # lean activations (memory-bound configs, e.g. dit_v4_5B with fewer checkpointed blocks):
@@ -404,54 +475,24 @@ class DiTBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
-        (xx, s2, wmod, mods, wqkv, wout, w1, w2, h1, r1, qkv, qkr, rq, o, lse, y1, x1, h2, r2, a_pre, a,
+        # the four weights are saved for autograd's modified-in-place check; they are read from ctx.params
+        (xx, s2, wmod, mods, _, _, _, _, h1, r1, qkv, qkr, rq, o, lse, y1, x1, h2, r2, a_pre, a,
          y2, kd, vd) = ctx.saved_tensors
         geo = ctx.geo
         B, T, d = ctx.shape
         M = B * T
         H, D, tpf = geo.H, geo.D, geo.tpf
-        a1, gg1, a2, gg2 = mods[:, :2 * d], mods[:, 2 * d:3 * d], mods[:, 3 * d:5 * d], mods[:, 5 * d:]
         dx2 = dout.reshape(M, d).to(BF16).contiguous()
         dm = torch.empty_like(mods)  # d mods, bf16 as the modulation Linears' output gradient
-        if x1 is None:  # lean
-            x1 = K.gate_resid(xx, y1, gg1, tpf)
-
         prm = ctx.params  # (wqkv, bqkv, wout, bout, w1, b1, w2, b2, 4 x (w, b) mod) Parameters: gradient sinks
 
-        # ---- MLP branch
-        dy2, _, dbf2 = K.gate_bwd(dx2, y2, gg2, tpf, dg_out=dm[:, 5 * d:])
-        db2 = bgrad_into(prm[7], dbf2)  # per-frame partials [F, d] -> bias gradient
-        sink_b1 = grad_sink(prm[5])
-        db1 = sink_b1 if sink_b1 is not None else torch.zeros(a_pre.shape[1], device=a_pre.device,
-                                                              dtype=torch.float32)
-        if a is None:  # lean: the dSiLU epilogue also emits a = silu(a_pre)
-            a = torch.empty_like(a_pre)
-            dapre = K.gemm(dy2, bf16_weight(w2), b_trans=True, epi=K.EPI_DSILU, aux=a_pre, colsum=db1, resid=a)
-        else:
-            dapre = K.gemm(dy2, bf16_weight(w2), b_trans=True, epi=K.EPI_DSILU, aux=a_pre, colsum=db1)  # + colsum
-        if sink_b1 is not None:
-            grad_done(prm[5])
-            db1 = None
-        dw2 = wgrad_into(prm[6], dy2, a)
-        del a
-        if h2 is None:
-            h2, _ = K.adaln_fwd(x1, a2[:, :d], a2[:, d:], tpf)
-        dw1 = wgrad_into(prm[4], dapre, h2)
-        del h2
-        dh2 = K.gemm(dapre, bf16_weight(w1), b_trans=True)
-        del dapre
-        if K.ADALN_GATE:  # the attention branch's gate backward fused onto the dx rows (bit for bit)
-            dx1, dy1, dbf1 = K.adaln_gate_bwd_into(dh2, x1, r2, a2[:, :d], tpf, dm[:, 3 * d:5 * d], dx2, y1, gg1,
-                                                   dm[:, 2 * d:3 * d])
-        else:
-            dx1 = K.adaln_bwd_into(dh2, x1, r2, a2[:, :d], tpf, dm[:, 3 * d:5 * d], dres=dx2)
-            dy1, _, dbf1 = K.gate_bwd(dx1, y1, gg1, tpf, dg_out=dm[:, 2 * d:3 * d])
-        del dh2, x1
+        # ---- MLP branch and the attention branch's gate
+        dx1, dy1, (dbout, dw1, db1, dw2, db2) = block_tail_bwd(dx2, xx, mods, dm, tpf, prm[2:8],
+                                                               (y1, x1, h2, r2, a_pre, a, y2))
 
         # ---- attention branch
-        dbout = bgrad_into(prm[3], dbf1)
         # dO and the attention backward's delta = rowsum(dO * O) in one launch (the GEMM epilogue)
-        do, delta = K.gemm_attn_delta(dy1, bf16_weight(wout), o, H, D, T)
+        do, delta = K.gemm_attn_delta(dy1, bf16_weight(prm[2]), o, H, D, T)
         dwout = wgrad_into(prm[2], dy1, o)
         del dy1
         if qkr is None:
@@ -484,14 +525,8 @@ class DiTBlockFn(torch.autograd.Function):
             grad_done(prm[1])
             dbqkv = None
         del qkr, q3, k3
-        if h1 is None:
-            h1, _ = K.adaln_fwd(xx, a1[:, :d], a1[:, d:], tpf)
-        dwqkv = wgrad_into(prm[0], dqkv, h1)
-        del h1
-        dh1 = K.gemm(dqkv, bf16_weight(wqkv), b_trans=True)
+        dx, dwqkv = block_head_bwd(dqkv, h1, xx, r1, mods, dm, tpf, prm[0], dx1)
         del dqkv
-        dx = K.adaln_bwd_into(dh1, xx, r1, a1[:, :d], tpf, dm[:, :2 * d], dres=dx1)
-        del dh1
 
         # ---- modulation: one dX GEMM against the stack onto the CondGrad of s; dW / db per fc
         ds = cond_grad_add(ctx.cg, dm, wmod, ctx.sshape) if ctx.needs_input_grad[1] else None
@@ -513,14 +548,9 @@ class DiTBlockFn(torch.autograd.Function):
                 dwqkv, dbqkv, dwout, dbout, dw1, db1, dw2, db2, *mgrads)
 
 
-_MOD_STACK_GEMM = os.environ.get("OWL_MOD_STACK_GEMM", "1") != "0"  # 0: four weight-gradient GEMMs (A/B)
-
-
 def _stacked_mod_sink(ws, d):
     """[6d, d] fp32 view over the four modulation weights' bucket views when GradReducer laid them
     out back to back in column order (DiTBlock tags them, utils/grad_reducer.py), else None."""
-    if not _MOD_STACK_GEMM:
-        return None
     sinks = [grad_sink(w) for w in ws]
     if any(v is None or not v.is_contiguous() for v in sinks):
         return None

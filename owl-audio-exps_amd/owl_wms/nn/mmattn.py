@@ -26,7 +26,8 @@ import torch
 from torch import nn
 
 from .. import kernels as K
-from .fused import bf16_weight, cond_silu, grad_done, grad_sink, linear
+from .fused import (bf16_weight, bgrad_into, block_head_bwd, block_tail, block_tail_bwd, cond_silu, grad_done, linear,
+                    wgrad_into)
 from .mlp import MLP
 from .rope import get_rope_cls
 
@@ -103,6 +104,25 @@ class _AudioLane:
                     t.record_stream(self.main)
 
 
+def _modality_slots(s):
+    """Where modality s's parameters stand among MMDiTBlockFn's sixteen (*w, and the gradients it
+    returns): its (qkv weight, bias), and its tail (out weight, bias, fc1 weight, bias, fc2 weight,
+    bias) in fused.block_tail's order.  *w = the two qkv pairs, the two out pairs, the two MLPs' four."""
+    return (2 * s, 2 * s + 1), (4 + 2 * s, 5 + 2 * s, 8 + 4 * s, 9 + 4 * s, 10 + 4 * s, 11 + 4 * s)
+
+
+def _modality_params(w, s):
+    qkv, tail = _modality_slots(s)
+    return tuple(w[i] for i in qkv), tuple(w[i] for i in tail)
+
+
+def _cast_weights(ws):
+    """Refresh the cached bf16 copies of ws (a cast after an optimizer step) on the caller's stream,
+    before a lane fork: the block functions then find them cached on whichever stream they run."""
+    for p in ws:
+        bf16_weight(p)
+
+
 class MMDiTBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, x1, c0, c1, geo, *w):
@@ -113,19 +133,19 @@ class MMDiTBlockFn(torch.autograd.Function):
         xs = (x0.reshape(-1, d), x1.reshape(-1, d))
         ms = (c0.reshape(nf, 6 * d), c1.reshape(nf, 6 * d))
         ns = (n0, n1)
-        W = [w[0:2], w[2:4]], [w[4:6], w[6:8]], [w[8:12], w[12:16]]  # qkv, out, mlp (fc1 w/b, fc2 w/b)
+        prm = [_modality_params(w, s) for s in range(2)]  # ((wqkv, bqkv), tail) per modality
         inplace = _in_place_ok(d, n0, n1, nf)
         lane = _AudioLane(x0.device, _lane_ok(inplace, nf, n1))
         h1, r1, qkv = [None, None], [None, None], [None, None]
         if inplace:  # each modality's qkv projection writes its rows of the joint frames directly
             qkvj = torch.empty(B * T, 3 * d, device=x0.device, dtype=BF16)
             qkv_dst = _joint_views(qkvj, n0, n1, 3 * d)
-        wq = [bf16_weight(W[0][s][0]) for s in range(2)]
+        wq = [bf16_weight(prm[s][0][0]) for s in range(2)]
         lane.fork()
         for s in (1, 0):  # audio first: its launches go to the side stream, then the video's run beside
             with lane.on(s):
                 h1[s], r1[s] = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
-                qkv[s] = K.gemm(h1[s], wq[s], bias=W[0][s][1], out=qkv_dst[s] if inplace else None)
+                qkv[s] = K.gemm(h1[s], wq[s], bias=prm[s][0][1], out=qkv_dst[s] if inplace else None)
         lane.mark(h1[1:] + r1[1:])
         lane.join()
         if not inplace:
@@ -137,22 +157,12 @@ class MMDiTBlockFn(torch.autograd.Function):
                             score_bound=K.qk_norm_bound(D))
         os_ = _joint_views(o.view(B * T, d), n0, n1, d) if inplace else K.frame_split(o.view(B * T, d), n0, n1)
         saved, outs = [None, None], [None, None]
-        wts = [[bf16_weight(W[1][s][0]), bf16_weight(W[2][s][0]), bf16_weight(W[2][s][2])] for s in range(2)]
+        _cast_weights(p for s in range(2) for p in prm[s][1][0::2])
         lane.fork()
         for s in (1, 0):
             with lane.on(s):
-                g1, g2 = ms[s][:, 2 * d:3 * d], ms[s][:, 5 * d:]
-                M = xs[s].shape[0]
-                y1 = torch.empty(M, d, device=x0.device, dtype=BF16)
-                x1s = K.gemm(os_[s], wts[s][0], bias=W[1][s][1], epi=K.EPI_GATE_RESID, aux=y1, gate=g1, tpf=ns[s],
-                             resid=xs[s])
-                h2, r2 = K.adaln_fwd(x1s, ms[s][:, 3 * d:4 * d], ms[s][:, 4 * d:5 * d], ns[s])
-                a_pre = torch.empty(M, W[2][s][0].shape[0], device=x0.device, dtype=BF16)
-                a = K.gemm(h2, wts[s][1], bias=W[2][s][1], epi=K.EPI_SILU, aux=a_pre)
-                y2 = torch.empty(M, d, device=x0.device, dtype=BF16)
-                outs[s] = K.gemm(a, wts[s][2], bias=W[2][s][3], epi=K.EPI_GATE_RESID, aux=y2, gate=g2, tpf=ns[s],
-                                 resid=x1s)
-                saved[s] = [xs[s], ms[s], h1[s], r1[s], y1, x1s, h2, r2, a_pre, a, y2]
+                outs[s], acts = block_tail(os_[s], xs[s], ms[s], ns[s], prm[s][1])
+                saved[s] = [xs[s], ms[s], h1[s], r1[s], *acts]  # acts: y1, x1, h2, r2, a_pre, a, y2
         lane.mark(saved[1][4:] + [outs[1]])
         lane.join()
         ctx.save_for_backward(qkvj, qkr, rq, o, lse, *saved[0], *saved[1], *w)
@@ -164,30 +174,16 @@ class MMDiTBlockFn(torch.autograd.Function):
     def backward(ctx, dout0, dout1):
         qkvj, qkr, rq, o, lse = ctx.saved_tensors[:5]
         st = [ctx.saved_tensors[5:16], ctx.saved_tensors[16:27]]
-        w = ctx.saved_tensors[27:]
         geo = ctx.geo
         B, T0, T1, d, T, nf = ctx.dims
         H, D, n0, n1 = geo.H, geo.D, geo.n0, geo.n1
         ns = (n0, n1)
-        dW = [None] * 16
-        prm = ctx.params
-        done = []  # parameters whose bucket view is complete, reported to the reducer on the main stream
-
-        def wgrad(i, dy, x):  # dW_i = dy^T x straight into the bucket view (beta 1) or returned
-            sink = grad_sink(prm[i])
-            if sink is None:
-                dW[i] = K.gemm_wgrad(dy, x)
-            else:
-                K.gemm(dy, x, a_trans=True, b_trans=True, out=sink, out_f32=True, beta=1.0)
-                done.append(prm[i])
-
-        def bgrad(i, rows):  # db_i = column sums of rows (bf16 rows or fp32 per-frame partials)
-            sink = grad_sink(prm[i])
-            if sink is None:
-                dW[i] = K.colsum(rows)
-            else:
-                K.colsum(rows, out=sink)
-                done.append(prm[i])
+        dW = [None] * 16  # in the order of *w; None where the gradient went into the parameter's bucket view
+        prm = [_modality_params(ctx.params, s) for s in range(2)]
+        slots = [_modality_slots(s) for s in range(2)]
+        # parameters whose bucket view is complete (fused.wgrad_into's done): a write may be on the side
+        # stream, so the reducer hears of it on the main stream after the join
+        done = []
 
         def report():  # after a lane join: every write above is ordered before the main stream's next work
             for q in done:
@@ -205,40 +201,19 @@ class MMDiTBlockFn(torch.autograd.Function):
         else:
             os_ = K.frame_split(o.view(B * T, d), n0, n1)
         dos, dx1s = [None, None], [None, None]
-        wts = [[bf16_weight(w[10 + 4 * s]), bf16_weight(w[8 + 4 * s]), bf16_weight(w[4 + 2 * s])] for s in range(2)]
+        _cast_weights(p for s in range(2) for p in prm[s][1][0::2])
         lane.fork()
         for s in (1, 0):
             with lane.on(s):
-                xs, ms, h1, r1, y1, x1s, h2, r2, a_pre, a, y2 = st[s]
-                dm = dcs[s]
-                # ---- MLP
-                dy2, _, dbf2 = K.gate_bwd(douts[s], y2, ms[:, 5 * d:], ns[s], dg_out=dm[:, 5 * d:])
-                bgrad(11 + 4 * s, dbf2)
-                i_b1 = 9 + 4 * s
-                sink_b1 = grad_sink(prm[i_b1])
-                cs = sink_b1 if sink_b1 is not None else torch.zeros(a_pre.shape[1], device=a_pre.device,
-                                                                     dtype=torch.float32)
-                dapre = K.gemm(dy2, wts[s][0], b_trans=True, epi=K.EPI_DSILU, aux=a_pre, colsum=cs)
-                if sink_b1 is not None:
-                    done.append(prm[i_b1])
-                else:
-                    dW[i_b1] = cs
-                wgrad(10 + 4 * s, dy2, a)
-                wgrad(8 + 4 * s, dapre, h2)
-                dh2 = K.gemm(dapre, wts[s][1], b_trans=True)
-                del dapre, dy2
-                if K.ADALN_GATE:  # + the attention output's gate backward on the dx rows (bit for bit)
-                    dx1, dy1, dbf1 = K.adaln_gate_bwd_into(dh2, x1s, r2, ms[:, 3 * d:4 * d], ns[s], dm[:, 3 * d:5 * d],
-                                                           douts[s], y1, ms[:, 2 * d:3 * d], dm[:, 2 * d:3 * d])
-                else:
-                    dx1 = K.adaln_bwd_into(dh2, x1s, r2, ms[:, 3 * d:4 * d], ns[s], dm[:, 3 * d:5 * d], dres=douts[s])
-                    dy1, _, dbf1 = K.gate_bwd(dx1, y1, ms[:, 2 * d:3 * d], ns[s], dg_out=dm[:, 2 * d:3 * d])
+                tail = prm[s][1]
+                dx1s[s], dy1, grads = block_tail_bwd(douts[s], st[s][0], st[s][1], dcs[s], ns[s], tail, st[s][4:],
+                                                     done.append)
                 # ---- attention output projection
-                bgrad(5 + 2 * s, dbf1)
-                dos[s] = K.gemm(dy1, wts[s][2], b_trans=True, out=do_dst[s] if inplace else None)
-                wgrad(4 + 2 * s, dy1, os_[s])
-                dx1s[s] = dx1
-        lane.mark([dW[i] for i in (6, 7, 12, 13, 14, 15)] + [dx1s[1]] + [dos[1]])  # audio's
+                dos[s] = K.gemm(dy1, bf16_weight(tail[0]), b_trans=True, out=do_dst[s] if inplace else None)
+                dwout = wgrad_into(tail[0], dy1, os_[s], done.append)
+                for i, g in zip(slots[s][1], (dwout,) + grads):  # dwout, dbout, dw1, db1, dw2, db2
+                    dW[i] = g
+        lane.mark([dW[i] for i in slots[1][1]] + [dx1s[1]] + [dos[1]])  # audio's
         lane.join()
         report()
         del os_
@@ -257,16 +232,15 @@ class MMDiTBlockFn(torch.autograd.Function):
         # the per-modality qkv gradients: views of the joint rows (in place) or split copies
         dqkv = _joint_views(dqkvj, n0, n1, 3 * d) if inplace else K.frame_split(dqkvj, n0, n1)
         dxs = [None, None]
-        wq = [bf16_weight(w[2 * s]) for s in range(2)]
+        _cast_weights(prm[s][0][0] for s in range(2))
         lane.fork()
         for s in (1, 0):
             with lane.on(s):
                 xs, ms, h1, r1 = st[s][:4]
-                bgrad(1 + 2 * s, dqkv[s])
-                wgrad(2 * s, dqkv[s], h1)
-                dh1 = K.gemm(dqkv[s], wq[s], b_trans=True)
-                dxs[s] = K.adaln_bwd_into(dh1, xs, r1, ms[:, :d], ns[s], dcs[s][:, :2 * d], dres=dx1s[s])
-        lane.mark([dW[3], dW[2], dxs[1], dcs[1]])
+                (wqkv, bqkv), (iw, ib) = prm[s][0], slots[s][0]
+                dW[ib] = bgrad_into(bqkv, dqkv[s], done.append)
+                dxs[s], dW[iw] = block_head_bwd(dqkv[s], h1, xs, r1, ms, dcs[s], ns[s], wqkv, dx1s[s], done.append)
+        lane.mark([dW[i] for i in slots[1][0]] + [dxs[1], dcs[1]])
         lane.join()
         report()
         return (dxs[0].view(B, T0, d), dxs[1].view(B, T1, d), dcs[0].view(B, nf // B, 6 * d),
@@ -303,16 +277,20 @@ class MMDiTBlock(nn.Module):
         H = cfg.n_heads
         n0 = cfg.sample_size ** 2
         geo = MMGeometry(H, cfg.d_model // H, n0, 1, block_mask, a.rope.cos, a.rope.sin)
-        ws = []
+        ws = [None] * 16
         for s in range(2):
-            ws += [a.qkv_projs[s].weight, a.qkv_projs[s].bias]
-        for s in range(2):
-            ws += [a.out_projs[s].weight, a.out_projs[s].bias]
-        for s in range(2):
-            m = self.mlps[s]
-            ws += [m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias]
+            qkv_at, tail_at = _modality_slots(s)
+            for i, p in zip(qkv_at + tail_at, self.qkv_params(s) + self.tail_params(s)):
+                ws[i] = p
         return MMDiTBlockFn.apply(x0.to(BF16).contiguous(), x1.to(BF16).contiguous(), cond0, cond1, geo, *ws)
 
+    def qkv_params(self, s):
+        return self.attn.qkv_projs[s].weight, self.attn.qkv_projs[s].bias
+
+    def tail_params(self, s):
+        """(wout, bout, w1, b1, w2, b2) of modality s: its parameters after the attention (fused.block_tail)"""
+        o, m = self.attn.out_projs[s], self.mlps[s]
+        return o.weight, o.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias
 
     def _forward_cached(self, x0, x1, cond0, cond1, block_mask, kv_cache):
         """MMDiTBlock.forward (mmattn.py:98-114) with MMAttn's cache path (mmattn.py:46-72)."""
@@ -329,7 +307,8 @@ class MMDiTBlock(nn.Module):
         qkv = []
         for s in range(2):
             h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
-            qkv.append(K.gemm(h, bf16_weight(a.qkv_projs[s].weight), bias=a.qkv_projs[s].bias))
+            wqkv, bqkv = self.qkv_params(s)
+            qkv.append(K.gemm(h, bf16_weight(wqkv), bias=bqkv))
         qkvj = K.frame_interleave(qkv[0], qkv[1], n0, n1)
         del qkv
         li = a.layer_idx
@@ -349,16 +328,7 @@ class MMDiTBlock(nn.Module):
         mask = block_mask if block_mask is not None else K.FrameMask(1, None, False, 0, None)
         o, _ = K.attn_fwd(q, k, v, H, D, mask, score_bound=K.qk_norm_bound(D))
         os_ = K.frame_split(o.view(B * T, d), n0, n1)
-        outs = []
-        for s in range(2):
-            x1s = K.gemm(os_[s], bf16_weight(a.out_projs[s].weight), bias=a.out_projs[s].bias, epi=K.EPI_GATE_RESID,
-                         gate=ms[s][:, 2 * d:3 * d], tpf=ns[s], resid=xs[s])
-            h2, _ = K.adaln_fwd(x1s, ms[s][:, 3 * d:4 * d], ms[s][:, 4 * d:5 * d], ns[s])
-            m = self.mlps[s]
-            a_pre = torch.empty(x1s.shape[0], m.fc1.weight.shape[0], device=x0.device, dtype=BF16)
-            act = K.gemm(h2, bf16_weight(m.fc1.weight), bias=m.fc1.bias, epi=K.EPI_SILU, aux=a_pre)
-            outs.append(K.gemm(act, bf16_weight(m.fc2.weight), bias=m.fc2.bias, epi=K.EPI_GATE_RESID,
-                               gate=ms[s][:, 5 * d:], tpf=ns[s], resid=x1s))
+        outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
         return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
 
 
