@@ -283,6 +283,29 @@ int owlk_mse(const void* pred, const void* tgt, long n, float gscale, void* dpre
 /* its backward: dpred = bf16((gscale * (pred - tgt)) * gout[0]) (gout NULL: 1), gscale = 2 / n for the mean */
 int owlk_mse_grad(const void* pred, const void* tgt, long n, float gscale, const float* gout, void* dpred,
                   void* stream);
+/* ---- Self-forcing distillation loss tails (csrc/distill.hip).  Tensors are [B, N, F] (F = C h w elements
+ * per frame, F % 8 == 0, 16-B aligned); video-side inputs are bf16 (in_f32 = 0) or fp32 (1), and so are
+ * the model velocities (v_f32 / pred_f32; the cores emit bf16); mask is one byte per frame [B, N]; every sum is fp32 per workgroup, finished in double in index order (no atomics:
+ * two calls give the same bits); loss is an fp32 scalar on the device.
+ *
+ * DMD loss (sf_vid_only.py:262-349, the tail after the three no-grad forwards): v_t = v_uncond +
+ * cfg_scale (v_cond - v_uncond) (v_uncond NULL: v_t = v_cond, the cfg_scale == 1 branch); norm_b = mean
+ * over sample b of |video - noisy + ts v_t|; g = nan_to_num(ts (v_t - v_critic) / norm_b) (NaN -> 0,
+ * +-inf -> +-FLT_MAX); M = the mask's true frames x F; loss = 0.5 sum_masked g^2 / M (NaN at M = 0);
+ * dvideo (the video's dtype) = g / M on the mask's frames, 0 elsewhere -- the gradient of
+ * 0.5 mse(video[mask], (video - g)[mask]) without its two float64 tensors.  ts fp32 [B, N];
+ * ws: owlk_dmd_loss_ws_bytes(B, N, F) bytes (fully written; no zeroing needed). */
+long owlk_dmd_loss_ws_bytes(long B, long N, long F);
+int owlk_dmd_loss(const void* video, const void* noisy, int in_f32, const void* v_cond, const void* v_uncond,
+                  const void* v_critic, int v_f32, const float* ts, const void* mask, long B, long N, long F,
+                  float cfg_scale, float* loss, void* dvideo, void* ws, long ws_bytes, void* stream);
+/* Critic loss (sf_vid_only.py:229-260): d = m (pred - (z - video)), m the frame's mask; loss = sum d^2 /
+ * (B N F) (masked-out frames count as zeros in the mean); dpred = gscale d in pred's dtype (bf16 from the
+ * cores: one rounding), gscale = 2 / (B N F) for the mean.  ws: owlk_critic_loss_ws_bytes(B N F) bytes. */
+long owlk_critic_loss_ws_bytes(long n);
+int owlk_critic_loss(const void* pred, int pred_f32, const void* z, const void* video, int in_f32,
+                     const void* mask, long B, long N, long F, float gscale, float* loss, void* dpred, void* ws,
+                     long ws_bytes, void* stream);
 /* out[n] += sum_r x[r, n] (bias gradients); x bf16 (x_f32 = 0) or fp32.  With ws (>=
  * owlk_colsum_ws_bytes(R, N) bytes, 16-B aligned) row splits store partial rows that one pass adds
  * in order (bitwise deterministic); without it the splits combine by fp32 atomics. */

@@ -61,6 +61,10 @@ _SIGS = {
     "owlk_unpatchify": [P, I, I, L, P, P],
     "owlk_mse": [P, P, L, F, P, P, I, P, P],
     "owlk_mse_grad": [P, P, L, F, P, P, P],
+    "owlk_dmd_loss_ws_bytes": [L, L, L],
+    "owlk_dmd_loss": [P, P, I, P, P, P, I, P, P, L, L, L, F, P, P, P, L, P],
+    "owlk_critic_loss_ws_bytes": [L],
+    "owlk_critic_loss": [P, I, P, P, I, P, L, L, L, F, P, P, P, L, P],
     "owlk_gate_resid": [P, L, P, L, P, L, L, L, I, P, L, P],
     "owlk_colsum_ws_bytes": [L, L],
     "owlk_colsum": [P, I, L, L, L, P, P, L, P],
@@ -81,6 +85,7 @@ _SIGS = {
 _RESTYPES = {n: ctypes.c_long for n in ("owlk_gemm_splitk_bytes", "owlk_gemm_ws_bytes", "owlk_gemm_ws_counter_bytes",
                                          "owlk_qk_rope_bwd_ws_bytes", "owlk_attn_bwd_fused_ws_bytes",
                                         "owlk_attn_decode_bwd_ws_bytes",
+                                        "owlk_dmd_loss_ws_bytes", "owlk_critic_loss_ws_bytes",
                                         "owlk_colsum_ws_bytes", "owlk_ns_iterate_ws_bytes",
                                         "owlk_newton_schulz_ws_bytes")}
 

@@ -67,6 +67,11 @@ class TrainingConfig:
     resume_ckpt: str = None
     teacher_ckpt: str = None
     teacher_cfg: str = None
+    student_ckpt: str = None
+    d_opt_kwargs: dict = None  # the critic's optimizer (self-forcing; None: opt_kwargs)
+    update_ratio: int = 5  # critic updates per student update (every reference distillation config)
+    rollout_steps: int = 1  # RolloutManager's defaults (sf_vid_only.py:113)
+    min_rollout_frames: int = 8
     sample_interval: int = 1000
     save_interval: int = 1000
     n_samples: int = 8

@@ -697,6 +697,69 @@ def mse_grad(pred, tgt, gout=None):
     return dpred
 
 
+def _frames3(name, video, others, want_dtype=None):
+    """[B, N, ...] tensors of one shape (and dtype) -> (B, N, F); a mismatch raises as a library refusal does"""
+    if video.dim() < 3:
+        raise RuntimeError(f"{name}: [B, N, ...] tensors expected (got {tuple(video.shape)})")
+    for n, t in others.items():
+        if t is None:
+            continue
+        if tuple(t.shape) != tuple(video.shape):
+            raise RuntimeError(f"{name}: {n} has shape {tuple(t.shape)}, video has {tuple(video.shape)}")
+        want = want_dtype.get(n, video.dtype) if want_dtype else video.dtype
+        if t.dtype != want:
+            raise RuntimeError(f"{name}: {n} must be {want} (got {t.dtype})")
+    B, N = video.shape[:2]
+    return B, N, video[0, 0].numel()
+
+
+def _frame_mask(name, mask, B, N):
+    if tuple(mask.shape) != (B, N):
+        raise RuntimeError(f"{name}: mask has shape {tuple(mask.shape)}, [B, N] = {(B, N)} expected")
+    return mask.to(torch.bool).contiguous().view(torch.uint8)  # one byte per frame, 0 / 1
+
+
+def dmd_loss(video, noisy, v_cond, v_uncond, v_critic, ts, mask, cfg_scale):
+    """The DMD loss tail (owlk_dmd_loss): video, noisy [B, N, ...] bf16 or fp32; v_cond, v_uncond (None:
+    no guidance), v_critic in one dtype, bf16 (the cores') or fp32; ts [B, N]; mask [B, N] bool -> (loss fp32
+    0-dim, dvideo in the video's dtype: d loss / d video, zero off the mask)."""
+    _in_dtype_flag(video, "video")
+    v_f32 = _in_dtype_flag(v_cond, "v_cond")
+    B, N, F_ = _frames3("dmd_loss", video, {"noisy": noisy, "v_cond": v_cond, "v_uncond": v_uncond,
+                                            "v_critic": v_critic},
+                        {"v_cond": v_cond.dtype, "v_uncond": v_cond.dtype, "v_critic": v_cond.dtype})
+    if tuple(ts.shape) != (B, N):
+        raise RuntimeError(f"dmd_loss: ts has shape {tuple(ts.shape)}, [B, N] = {(B, N)} expected")
+    video, noisy, v_cond, v_critic = (t.contiguous() for t in (video, noisy, v_cond, v_critic))
+    v_uncond = v_uncond.contiguous() if v_uncond is not None else None
+    ts, m = ts.to(F32).contiguous(), _frame_mask("dmd_loss", mask, B, N)
+    nws = lib().owlk_dmd_loss_ws_bytes(B, N, F_)
+    ws = torch.empty(max(nws, 4) // 4, device=video.device, dtype=F32)
+    loss = torch.empty((), device=video.device, dtype=F32)
+    dvideo = torch.empty_like(video)
+    call("owlk_dmd_loss", ptr(video), ptr(noisy), _in_dtype_flag(video, "video"), ptr(v_cond), ptr(v_uncond),
+         ptr(v_critic), v_f32, ptr(ts), ptr(m), B, N, F_, float(cfg_scale), ptr(loss), ptr(dvideo), ptr(ws), nws, stream())
+    return loss, dvideo
+
+
+def critic_loss(pred, z, video, mask, grad_scale=1.0):
+    """The critic loss tail (owlk_critic_loss): pred bf16 (the cores') or fp32, z and video bf16 or fp32, all
+    [B, N, ...]; mask [B, N] bool -> (loss fp32 0-dim = mean of (m (pred - (z - video)))^2, dpred in pred's
+    dtype = d loss / d pred)."""
+    _in_dtype_flag(video, "video")
+    B, N, F_ = _frames3("critic_loss", video, {"z": z, "pred": pred}, {"pred": pred.dtype})
+    pred, z, video, m = pred.contiguous(), z.contiguous(), video.contiguous(), _frame_mask("critic_loss", mask, B, N)
+    n = B * N * F_
+    nws = lib().owlk_critic_loss_ws_bytes(n)
+    ws = torch.empty(max(nws, 4) // 4, device=video.device, dtype=F32)
+    loss = torch.empty((), device=video.device, dtype=F32)
+    dpred = torch.empty_like(pred)
+    call("owlk_critic_loss", ptr(pred), _in_dtype_flag(pred, "pred"), ptr(z), ptr(video),
+         _in_dtype_flag(video, "video"), ptr(m), B, N, F_,
+         float(2.0 * grad_scale / n), ptr(loss), ptr(dpred), ptr(ws), nws, stream())
+    return loss, dpred
+
+
 def colsum(x, out=None):
     """fp32 column sums of a 2-D row-major view (or a 3-D frame_rows view), added onto out
     (deterministic: row-split partials in a workspace, summed in order)."""

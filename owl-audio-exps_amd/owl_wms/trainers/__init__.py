@@ -11,8 +11,10 @@ def get_trainer_cls(trainer_id):
     if trainer_id == "av":
         from .rft_trainer import AVRFTTrainer
         return AVRFTTrainer
-    raise NotImplementedError(f"trainer {trainer_id!r}: the distillation trainer classes are not built (SURVEY.md "
-                              "§2.1).  Their core is: trainers/self_forcing.py has the self-forcing rollout "
-                              "(RolloutManager, gradients through the KV-cache decode step) and the critic / DMD "
-                              "losses; the trainer class around them (teacher checkpoint, VAE decoder, EMA, "
-                              "logging) is not")
+    if trainer_id == "sforce_vid":
+        from .sf_trainer import SelfForceTrainer
+        return SelfForceTrainer
+    raise NotImplementedError(f"trainer {trainer_id!r}: of the distillation trainers only the self-forcing one is "
+                              "built ('sforce_vid', trainers/sf_trainer.py over the rollout and the critic / DMD "
+                              "losses of trainers/self_forcing.py); 'causvid_vid' and 'ode_distill_vid' are not "
+                              "(SURVEY.md §2.1)")

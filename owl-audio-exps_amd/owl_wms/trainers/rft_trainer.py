@@ -30,7 +30,67 @@ from ..utils.logging import LogHelper
 from .base import BaseTrainer
 
 
-class RFTTrainer(BaseTrainer):
+class LatentEval:
+    """The eval path of rft_trainer.py:155-170 / :243-280, shared by the trainers that sample with an EMA
+    core (RFTTrainer, sf_trainer.SelfForceTrainer): a sample loader and a sampler from the config, one
+    sampled batch, summary statistics of its latents."""
+
+    def eval_core(self):
+        """the GameRFTCore the sampler runs"""
+        return self.get_module(ema=True).core
+
+    def eval_setup(self):
+        """sample loader + sampler (rft_trainer.py:155-170); None when the config names no sampler."""
+        sid = self.train_cfg.get("sampler_id")
+        if not sid:
+            return None, None
+        n = (int(self.train_cfg.get("n_samples") or 1) + self.world_size - 1) // self.world_size
+        kw = dict(self.train_cfg.get("sample_data_kwargs") or {})
+        sample_loader = iter(get_loader(self.train_cfg.get("sample_data_id") or "synthetic", n,
+                                        model_cfg=self.model_cfg, **kw))
+        skw = dict(self.train_cfg.get("sampler_kwargs") or {})
+        self.sampler_only_return_generated = bool(skw.pop("only_return_generated", False))
+        return sample_loader, get_sampler_cls(sid)(**skw)
+
+    def _gather_concat_cpu(self, t, dim=0):
+        if self.world_size == 1:
+            return t.cpu()
+        if self.rank == 0:
+            parts, scratch = [t.cpu()], torch.empty_like(t)
+            for src in range(1, self.world_size):
+                dist.recv(scratch, src=src)
+                parts.append(scratch.cpu())
+            return torch.cat(parts, dim=dim)
+        dist.send(t, dst=0)
+
+    @torch.no_grad()
+    def eval_step(self, sample_loader, sampler):
+        ema_core = self.eval_core()
+        vid, mouse, btn = [x.cuda() for x in next(sample_loader)[:3]]
+        mouses, btns = [mouse], [btn]
+        for _ in range(15):
+            _, m, b = [x.cuda() for x in next(sample_loader)[:3]]
+            mouses.append(m)
+            btns.append(b)
+        mouse, button = batch_permute_to_length(torch.cat(mouses), torch.cat(btns), sampler.num_frames + vid.size(1))
+        mouse, button = mouse[:vid.size(0)], button[:vid.size(0)]
+        vid = vid / self.train_cfg.vae_scale
+        latent = sampler(ema_core, vid, mouse, button)
+        if self.sampler_only_return_generated:
+            latent = latent[:, vid.size(1):]
+        out = {"eval/samples": latent.shape[0] * self.world_size, "eval/frames": latent.shape[1],
+               "eval/latent_std": latent.float().std().item()}
+        if self.train_cfg.get("eval_sample_dir"):
+            full = self._gather_concat_cpu(latent)
+            if self.rank == 0:
+                d = Path(self.train_cfg.eval_sample_dir)
+                d.mkdir(parents=True, exist_ok=True)
+                torch.save(full, d / f"vid.{self.total_step_counter}.pt")
+        self.barrier()  # the reference's unconditional dist.barrier() (App. A.4), guarded for 1 rank
+        return out if self.rank == 0 else None
+
+
+class RFTTrainer(LatentEval, BaseTrainer):
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.model = get_model_cls(self.model_cfg.model_id)(self.model_cfg).train()
@@ -103,57 +163,6 @@ class RFTTrainer(BaseTrainer):
         data_id = self.train_cfg.get("data_id") or "synthetic"
         kw.setdefault("batch_columns", ["depth_latent", "mouse", "buttons"])
         return get_loader(data_id, self.train_cfg.batch_size, model_cfg=self.model_cfg, **kw)
-
-    # ------------------------------------------------------------------ eval (rft_trainer.py:243-280)
-    def eval_setup(self):
-        """sample loader + sampler (rft_trainer.py:155-170); None when the config names no sampler."""
-        sid = self.train_cfg.get("sampler_id")
-        if not sid:
-            return None, None
-        n = (int(self.train_cfg.get("n_samples") or 1) + self.world_size - 1) // self.world_size
-        kw = dict(self.train_cfg.get("sample_data_kwargs") or {})
-        sample_loader = iter(get_loader(self.train_cfg.get("sample_data_id") or "synthetic", n,
-                                        model_cfg=self.model_cfg, **kw))
-        skw = dict(self.train_cfg.get("sampler_kwargs") or {})
-        self.sampler_only_return_generated = bool(skw.pop("only_return_generated", False))
-        return sample_loader, get_sampler_cls(sid)(**skw)
-
-    def _gather_concat_cpu(self, t, dim=0):
-        if self.world_size == 1:
-            return t.cpu()
-        if self.rank == 0:
-            parts, scratch = [t.cpu()], torch.empty_like(t)
-            for src in range(1, self.world_size):
-                dist.recv(scratch, src=src)
-                parts.append(scratch.cpu())
-            return torch.cat(parts, dim=dim)
-        dist.send(t, dst=0)
-
-    @torch.no_grad()
-    def eval_step(self, sample_loader, sampler):
-        ema_core = self.get_module(ema=True).core
-        vid, mouse, btn = [x.cuda() for x in next(sample_loader)[:3]]
-        mouses, btns = [mouse], [btn]
-        for _ in range(15):
-            _, m, b = [x.cuda() for x in next(sample_loader)[:3]]
-            mouses.append(m)
-            btns.append(b)
-        mouse, button = batch_permute_to_length(torch.cat(mouses), torch.cat(btns), sampler.num_frames + vid.size(1))
-        mouse, button = mouse[:vid.size(0)], button[:vid.size(0)]
-        vid = vid / self.train_cfg.vae_scale
-        latent = sampler(ema_core, vid, mouse, button)
-        if self.sampler_only_return_generated:
-            latent = latent[:, vid.size(1):]
-        out = {"eval/samples": latent.shape[0] * self.world_size, "eval/frames": latent.shape[1],
-               "eval/latent_std": latent.float().std().item()}
-        if self.train_cfg.get("eval_sample_dir"):
-            full = self._gather_concat_cpu(latent)
-            if self.rank == 0:
-                d = Path(self.train_cfg.eval_sample_dir)
-                d.mkdir(parents=True, exist_ok=True)
-                torch.save(full, d / f"vid.{self.total_step_counter}.pt")
-        self.barrier()  # the reference's unconditional dist.barrier() (App. A.4), guarded for 1 rank
-        return out if self.rank == 0 else None
 
     # ------------------------------------------------------------------ training loop
     def train(self):

@@ -4,8 +4,9 @@ RolloutManager 112-225, get_critic_loss 229-260, get_dmd_loss 262-349).
 A rollout caches a context window without gradient, then generates frames one at a time against the
 KV cache; the LAST Euler step of each frame carries a gradient through the decode step (the
 differentiable KV-cache decode block, nn/fused.DiTBlockFn with a decode geometry), everything else runs
-without one.  The trainer classes built on these (teacher checkpoint, VAE decoder bridge, EMA,
-wandb) are not part of this package; ``get_trainer_cls`` says so.
+without one.  The trainer built on these is trainers/sf_trainer.py (``sforce_vid``).  On the GPU the two
+losses' element-wise tails are the libowlk kernels of csrc/distill.hip (``fused``), one deterministic
+fp32 pass each; the torch tails stay for other devices and dtypes.
 
 Differences from the reference, on purpose:
 * no "warmup call" before the context pass (sf_vid_only.py:154): it works around autocast's
@@ -145,38 +146,98 @@ def _loss_draws(video, noise):
     return ts, z, lerp_batched(video, z, ts)
 
 
-def get_critic_loss(student, critic, video, mouse, btn, rollout_manager, noise_source=None):
-    """sf_vid_only.py:229-260: the critic learns the flow of the student's rollouts (no gradient to
-    the student): mse of its velocity against z - video on the generated frames; the masked-out
-    frames count as zeros in the mean."""
-    noise = noise_source if noise_source is not None else rollout_manager.noise_source
-    with torch.no_grad():
-        video, mouse, btn, grad_mask = rollout_manager.get_rollouts(model=student, video=video, mouse=mouse, btn=btn)
-        ts, z, noisy = _loss_draws(video, noise)
-        target = z - video
-    pred = critic(noisy, ts, mouse, btn)
+def _critic_tail(pred, z, video, grad_mask):
+    """the reference's tail (sf_vid_only.py:250-260) in torch, in the tensors' own dtype"""
     m = _per_frame(grad_mask)
-    return F.mse_loss(pred * m, target * m)
+    return F.mse_loss(pred * m, (z - video) * m)
 
 
-def get_dmd_loss(student, critic, teacher, video, mouse, btn, rollout_manager, cfg_scale=1.5, noise_source=None):
-    """sf_vid_only.py:262-349: distribution-matching loss of the student's rollout.  The gradient
-    direction (critic's denoised estimate - teacher's, the teacher with classifier-free guidance), scaled
-    per sample by mean |video - teacher estimate|, becomes a fixed double-precision target video - grad;
-    0.5 mse against it over the generated frames then has exactly that gradient."""
-    noise = noise_source if noise_source is not None else rollout_manager.noise_source
-    video, mouse, btn, grad_mask = rollout_manager.get_rollouts(model=student, video=video, mouse=mouse, btn=btn)
+def _dmd_tail(video, noisy, ts, v_cond, v_uncond, v_critic, grad_mask, cfg_scale):
+    """the reference's tail (sf_vid_only.py:300-349) in torch: v_uncond None is its cfg_scale == 1 branch"""
     with torch.no_grad():
-        ts, z, noisy = _loss_draws(video, noise)
-        v_teacher = teacher(noisy, ts, mouse, btn)
-        if cfg_scale != 1.0:
-            v_uncond = teacher(noisy, ts, torch.zeros_like(mouse), torch.zeros_like(btn))
-            v_teacher = v_uncond + cfg_scale * (v_teacher - v_uncond)
-        v_critic = critic(noisy, ts, mouse, btn)
-
+        v_teacher = v_cond if v_uncond is None else v_uncond + cfg_scale * (v_cond - v_uncond)
         mu_teacher = noisy - _per_frame(ts) * v_teacher
         mu_critic = noisy - _per_frame(ts) * v_critic
         normalizer = torch.abs(video - mu_teacher).mean(dim=[1, 2, 3, 4], keepdim=True)
         grad = torch.nan_to_num((mu_critic - mu_teacher) / normalizer, nan=0.0)
         target = (video.double() - grad.double()).detach()[grad_mask]
     return 0.5 * F.mse_loss(video[grad_mask].double(), target, reduction="mean")
+
+
+class _CriticLossFn(torch.autograd.Function):
+    """owlk_critic_loss: the loss and d loss / d pred from one pass; backward scales the kept gradient by
+    the incoming one on the device"""
+
+    @staticmethod
+    def forward(ctx, pred, z, video, grad_mask):
+        from .. import kernels as K
+        loss, dpred = K.critic_loss(pred, z, video, grad_mask)
+        ctx.save_for_backward(dpred)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dpred, = ctx.saved_tensors
+        return dpred * grad_output, None, None, None
+
+
+class _DMDLossFn(torch.autograd.Function):
+    """owlk_dmd_loss: the loss and d loss / d video (zero off the generated frames) in two passes"""
+
+    @staticmethod
+    def forward(ctx, video, noisy, ts, v_cond, v_uncond, v_critic, grad_mask, cfg_scale):
+        from .. import kernels as K
+        loss, dvideo = K.dmd_loss(video, noisy, v_cond, v_uncond, v_critic, ts, grad_mask, cfg_scale)
+        ctx.save_for_backward(dvideo)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        dvideo, = ctx.saved_tensors
+        return (dvideo * grad_output).to(dvideo.dtype), None, None, None, None, None, None, None
+
+
+def _use_kernels(fused, video):
+    """fused=None: the libowlk tails for a CUDA rollout in bf16 or fp32, the torch tails otherwise (the
+    CPU formula tests run in float64); False forces torch; True insists on the kernels"""
+    ok = video.is_cuda and video.dtype in (torch.bfloat16, torch.float32)
+    if fused and not ok:
+        raise RuntimeError(f"fused distillation losses need a CUDA rollout in bf16 or fp32 (got {video.device}, "
+                           f"{video.dtype})")
+    return ok if fused is None else bool(fused)
+
+
+def get_critic_loss(student, critic, video, mouse, btn, rollout_manager, noise_source=None, fused=None):
+    """sf_vid_only.py:229-260: the critic learns the flow of the student's rollouts (no gradient to
+    the student): mse of its velocity against z - video on the generated frames; the masked-out
+    frames count as zeros in the mean.  The tail is owlk_critic_loss on the GPU (``fused``: _use_kernels)."""
+    noise = noise_source if noise_source is not None else rollout_manager.noise_source
+    with torch.no_grad():
+        video, mouse, btn, grad_mask = rollout_manager.get_rollouts(model=student, video=video, mouse=mouse, btn=btn)
+        ts, z, noisy = _loss_draws(video, noise)
+    pred = critic(noisy, ts, mouse, btn)
+    if _use_kernels(fused, video):
+        return _CriticLossFn.apply(pred, z, video, grad_mask)
+    return _critic_tail(pred, z, video, grad_mask)
+
+
+def get_dmd_loss(student, critic, teacher, video, mouse, btn, rollout_manager, cfg_scale=1.5, noise_source=None,
+                 fused=None):
+    """sf_vid_only.py:262-349: distribution-matching loss of the student's rollout.  The gradient
+    direction (critic's denoised estimate - teacher's, the teacher with classifier-free guidance), scaled
+    per sample by mean |video - teacher estimate|, becomes a fixed double-precision target video - grad;
+    0.5 mse against it over the generated frames then has exactly that gradient.  On the GPU
+    (``fused``: _use_kernels) owlk_dmd_loss forms that loss and gradient directly, in fp32 from the
+    loaded values."""
+    noise = noise_source if noise_source is not None else rollout_manager.noise_source
+    video, mouse, btn, grad_mask = rollout_manager.get_rollouts(model=student, video=video, mouse=mouse, btn=btn)
+    with torch.no_grad():
+        ts, z, noisy = _loss_draws(video, noise)
+        v_cond = teacher(noisy, ts, mouse, btn)
+        v_uncond = None
+        if cfg_scale != 1.0:
+            v_uncond = teacher(noisy, ts, torch.zeros_like(mouse), torch.zeros_like(btn))
+        v_critic = critic(noisy, ts, mouse, btn)
+    if _use_kernels(fused, video):
+        return _DMDLossFn.apply(video, noisy, ts, v_cond, v_uncond, v_critic, grad_mask, float(cfg_scale))
+    return _dmd_tail(video, noisy, ts, v_cond, v_uncond, v_critic, grad_mask, cfg_scale)

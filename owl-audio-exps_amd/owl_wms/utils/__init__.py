@@ -20,6 +20,13 @@ def freeze(module):
         p.requires_grad = False
 
 
+def unfreeze(module):
+    if module is None:
+        return
+    for p in module.parameters():
+        p.requires_grad = True
+
+
 _PREFIX = re.compile(r'^(?:(?:_orig_mod\.|module\.)+)?([^.]+\.)?(?:(?:_orig_mod\.|module\.)+)?')
 
 
