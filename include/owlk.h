@@ -148,6 +148,16 @@ int owlk_qk_rope_fwd_kv_dev(const void* qkv, long ldq, long T, long L, int H, in
                             const float* sinb, long ld_tab, long n_tab, const long* state, void* qo, long ldqo,
                             long sqo, void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
                             void* stream);
+/* MMDiT decode form (mmattn.py:46-86): the joint frames [n0 video | n1 audio] read straight from the
+ * two modalities' qkv GEMM outputs (joint row r of frame f of batch b: video row (b nf + f) n0 + r for
+ * r < n0, else audio row (b nf + f) n1 + r - n0), table row tab_off + f (n0 + n1) + r.  q goes to a
+ * joint [B, nf (n0 + n1), H D] destination, k and v to the KV cache's slots, each with its own row
+ * and batch stride; any nf >= 1.  The same bits as owlk_frame_mux -> owlk_qk_rope_fwd -> cache copy.
+ * Returns 1 when a position lies past the n_tab table rows. */
+int owlk_mm_qk_rope_fwd_kv(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf, int n0, int n1,
+                           int H, int D, const float* cosb, const float* sinb, long ld_tab, long n_tab,
+                           long tab_off, void* qo, long ldqo, long sqo, void* ko, long ldko, long sko, void* vo,
+                           long ldvo, long svo, void* stream);
 int owlk_qk_rope_bwd(const void* dqk, long ldd, const void* qkv, long ldq, long T, int H, int D,
                      const float* cosb, const float* sinb, long ld_tab, long n_tab, long tab_off, long tpos_div,
                      const float* rstd, void* dqkv, long ldg, void* stream);
@@ -190,6 +200,16 @@ int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const void* kbuf, lo
                          const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse, long B,
                          int H, long Lq, int head_dim, float scale, float score_bound, const long* state,
                          long Lnew, long window_tokens, long cap, void* stream);
+/* Joint-frame decode attention (mmattn.py:46-86, one new MMDiT frame against the cache): per (batch,
+ * head) the n0 + n1 <= 80 query rows of q [B, n0 + n1, H D] (row stride ldq, batch stride sqb),
+ * unmasked over Lkv key rows k / v (pointer + strides: [cache | new], or its last window rows for a
+ * windowed layer).  The video rows of the output go to o0 [B n0, H D], the audio rows to o1
+ * [B n1, H D] (the two out-projections' operands; no frame split follows).  head_dim 64, bounded
+ * softmax (score_bound > 0) only; lse [B, H, n0 + n1] base 2 as owlk_attn_fwd's, or null. */
+int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, const void* k, long ldk, long skb, const void* v,
+                               long ldv, long svb, void* o0, long ldo0, void* o1, long ldo1, float* lse, long B,
+                               int H, int n0, int n1, long Lkv, int head_dim, float scale, float score_bound,
+                               void* stream);
 /* delta[b, h, t] = sum_d dO * O (fp32), the backward's row constant */
 int owlk_attn_delta(const void* o, const void* dout, long ld, long B, long L, int H, int D, float* delta,
                     void* stream);

@@ -997,6 +997,193 @@ __global__ __launch_bounds__(256, 1) void attn_fwd16_split_k(FwdP p, const long*
   if ((threadIdx.x & 3) == 0) p.lse[(b * p.H + head) * p.Lq + q] = l > 0.f ? __log2f(l) : -INFINITY;
 }
 
+// Joint-frame decode (MMDiT, mmattn.py:46-86): attn_fwd16_split_k<64> with five 16-query tiles, for
+// one joint frame of Lq = n0 + n1 <= 80 rows ([n0 video | n1 audio], 65 at mmdit_v2) against Lkv key
+// rows [cache | frame], unmasked, bounded softmax.  The 4 waves share the queries and split the
+// 64-key tiles exactly as there (private 2-slot LDS-DMA rings, no barrier in the sweep, partials
+// added in wave order); a wave with no tile adds zeros.  The combine writes the video rows to o0
+// [B n0, d] and the audio rows to o1 [B n1, d] (the two out-projections' operands), so no frame_split
+// follows.  Query rows >= Lq are zeros in registers and never written; key rows >= Lkv are the
+// clamped last row in LDS (tile_glds) and masked to -inf, so nothing past either extent is touched
+// in HBM.  One wave per SIMD: 80 fp32 accumulator registers for O^T, 40 for the queries.
+struct JointP {
+  const bf16 *q, *k, *v;
+  bf16 *o0, *o1;
+  float* lse;  // [B, H, Lq] base 2, or null
+  long ldq, sqb, ldk, skb, ldv, svb, ldo0, ldo1;
+  long Lq, Lkv;
+  int n0, n1, H;
+  float scale_log2;
+};
+
+struct JointCfg {
+  static constexpr int D = 64, NQT = 5, QR = 16 * NQT;  // 80 query rows
+  using C = DecCfg<64>;
+  static constexpr int COMB = 4 * QR * C::OLD * 4 + 4 * QR * 4;  // [4][80][68] fp32 + [4][80] row sums
+  static constexpr int SMEM = 4 * C::RING > COMB ? 4 * C::RING : COMB;
+};
+
+__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointP p) {
+  using C = DecCfg<64>;
+  constexpr int D = 64, KTD = C::KTD, NQT = JointCfg::NQT, QR = JointCfg::QR;
+  __shared__ __attribute__((aligned(16))) char smem[JointCfg::SMEM];
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = lane & 15, g = lane >> 4;
+  const long b = blockIdx.z;
+  const int head = blockIdx.y;
+  const bf16* Q = p.q + b * p.sqb + head * D;
+  const bf16* K = p.k + b * p.skb + head * D;
+  const bf16* V = p.v + b * p.svb + head * D;
+  const int ntiles = (int)((p.Lkv + KTD - 1) / KTD);
+  const int nt = ntiles > w ? (ntiles - w + 3) / 4 : 0;  // this wave's tiles: w + 4 i
+
+  bf16x8 qf[NQT][C::NKD];
+#pragma unroll
+  for (int t5 = 0; t5 < NQT; ++t5) {
+    const int qr = 16 * t5 + c;
+#pragma unroll
+    for (int kd = 0; kd < C::NKD; ++kd) {
+      bf16x8 qv = qr < p.Lq ? *(const bf16x8*)(Q + qr * p.ldq + 32 * kd + 8 * g) : bf16x8{};
+      float f[8];
+      unpack8(qv, f);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) f[j] *= p.scale_log2;
+      qf[t5][kd] = pack8(f);
+    }
+  }
+  f32x4 o[C::NDS][NQT];
+#pragma unroll
+  for (int ds = 0; ds < C::NDS; ++ds)
+#pragma unroll
+    for (int t5 = 0; t5 < NQT; ++t5) o[ds][t5] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float lrow[NQT];
+#pragma unroll
+  for (int t5 = 0; t5 < NQT; ++t5) lrow[t5] = 0.f;
+
+  char* ring = smem + w * C::RING;
+  auto issue = [&](int i) {  // the wave's i-th tile (key tile w + 4 i), all KTD rows by this wave
+    const long c0 = (long)(w + 4 * i) * KTD;
+    char* buf = ring + (i & 1) * C::TILEB;
+#pragma unroll
+    for (int q4 = 0; q4 < KTD / 16; ++q4) {
+      tile_glds<SW_ROW>(buf, K, p.ldk, c0, p.Lkv, q4, lane);
+      tile_glds<SW_DUAL>(buf + C::SUBK, V, p.ldv, c0, p.Lkv, q4, lane);
+    }
+  };
+  if (nt > 0) issue(0);
+  if (nt > 1) issue(1);
+  for (int i = 0; i < nt; ++i) {
+    if (i + 1 < nt)
+      vmcnt<C::OPS>();  // tile i landed (this wave's own DMA: no barrier), i + 1 in flight
+    else
+      vmcnt<0>();
+    const long c0 = (long)(w + 4 * i) * KTD;
+    const char* lk = ring + (i & 1) * C::TILEB;
+    const char* lv = lk + C::SUBK;
+    const bool ragged = c0 + KTD > p.Lkv;
+#pragma unroll
+    for (int kc = 0; kc < C::NKC; ++kc) {
+      f32x4 st[2][NQT];
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int t5 = 0; t5 < NQT; ++t5) st[kk][t5] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kd = 0; kd < C::NKD; ++kd)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk) {
+          const bf16x8 ak = frag_row16<SW_ROW>(lk, 32 * kc + 16 * kk, kd, lane);
+#pragma unroll
+          for (int t5 = 0; t5 < NQT; ++t5)
+            st[kk][t5] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ak, qf[t5][kd], st[kk][t5], 0, 0, 0);
+        }
+      if (ragged) {
+        __asm__ volatile("");  // keep the uniform branch a branch
+        const long kb0 = c0 + 32 * kc + 4 * g;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (kb0 + 16 * kk + r >= p.Lkv)
+#pragma unroll
+              for (int t5 = 0; t5 < NQT; ++t5) st[kk][t5][r] = -INFINITY;
+      }
+      bf16x8 pf[NQT];
+#pragma unroll
+      for (int t5 = 0; t5 < NQT; ++t5) {
+        float ps0 = 0.f, ps1 = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float pv = __builtin_amdgcn_exp2f(st[kk][t5][r]);
+            st[kk][t5][r] = pv;
+            if (r & 1)
+              ps1 += pv;
+            else
+              ps0 += pv;
+          }
+        lrow[t5] += ps0 + ps1;
+        pf[t5] = pack_perm(st[0][t5], st[1][t5]);
+      }
+#pragma unroll
+      for (int ds = 0; ds < C::NDS; ++ds) {
+        const bf16x8 vt = frag_tr16<SW_DUAL>(lv, 32 * kc, ds, lane);
+#pragma unroll
+        for (int t5 = 0; t5 < NQT; ++t5)
+          o[ds][t5] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pf[t5], o[ds][t5], 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (i + 2 < nt) {
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this slot's reads retired before its refill
+      issue(i + 2);
+    }
+  }
+  // combine: wave partials (O^T tiles: d = 16 ds + 4 g + r, query 16 t5 + c) -> LDS [w][q][d], then
+  // each thread sums 16 columns of one query over the 4 waves in order (320 items over 256 threads)
+  vmcnt<0>();
+  __syncthreads();
+  constexpr int OLD = C::OLD;
+  float* img = (float*)smem;                        // [4][80][OLD]
+  float* lsum = (float*)(smem + 4 * QR * OLD * 4);  // [4][80]
+#pragma unroll
+  for (int t5 = 0; t5 < NQT; ++t5) {
+    const int q = 16 * t5 + c;
+#pragma unroll
+    for (int ds = 0; ds < C::NDS; ++ds)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) img[(w * QR + q) * OLD + 16 * ds + 4 * g + r] = o[ds][t5][r];
+    float lt = lrow[t5] + __shfl_xor(lrow[t5], 16, 64);
+    lt += __shfl_xor(lt, 32, 64);
+    if (g == 0) lsum[w * QR + q] = lt;
+  }
+  __syncthreads();
+  for (int item = threadIdx.x; item < 4 * QR; item += 256) {
+    const int q = item >> 2, d0 = 16 * (item & 3);
+    if (q >= p.Lq) continue;
+    float l = 0.f;
+#pragma unroll
+    for (int ww = 0; ww < 4; ++ww) l += lsum[ww * QR + q];
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+    bf16* O = (q < p.n0 ? p.o0 + (b * p.n0 + q) * p.ldo0 : p.o1 + (b * p.n1 + (q - p.n0)) * p.ldo1) + head * D + d0;
+#pragma unroll
+    for (int h8 = 0; h8 < 2; ++h8) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = 0.f;
+#pragma unroll
+      for (int ww = 0; ww < 4; ++ww)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] += img[(ww * QR + q) * OLD + d0 + 8 * h8 + e];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] *= inv;
+      *(bf16x8*)(O + 8 * h8) = pack8(v);
+    }
+    if ((item & 3) == 0 && p.lse) p.lse[(b * p.H + head) * p.Lq + q] = l > 0.f ? __log2f(l) : -INFINITY;
+  }
+}
+
 template <int D>
 void launch_fwd(const FwdP& p, dim3 grid, hipStream_t s) {
   static const int two = getenv("OWLK_FWD2") ? atoi(getenv("OWLK_FWD2")) : 1;
@@ -1159,4 +1346,31 @@ extern "C" int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const voi
     hipLaunchKernelGGL(attn_fwd16_split_k<128>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                        p, state, Lnew, window_tokens, cap);
   return owlk::check_launch("attn_decode_fwd");
+}
+
+extern "C" int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, const void* k, long ldk, long skb,
+                                          const void* v, long ldv, long svb, void* o0, long ldo0, void* o1, long ldo1,
+                                          float* lse, long B, int H, int n0, int n1, long Lkv, int head_dim,
+                                          float scale, float score_bound, void* stream) {
+  OWLK_REQUIRE(head_dim == 64, "attn_decode_joint_fwd: head_dim %d not built (64)", head_dim);
+  OWLK_REQUIRE(B > 0 && H > 0 && n0 > 0 && n1 > 0 && Lkv > 0 && B <= 65535 && H <= 65535,
+               "attn_decode_joint_fwd: bad sizes");
+  OWLK_REQUIRE((long)n0 + n1 <= JointCfg::QR, "attn_decode_joint_fwd: one joint frame of at most %d rows (got %ld)",
+               JointCfg::QR, (long)n0 + n1);
+  OWLK_REQUIRE(score_bound > 0.f && score_bound * scale < 40.f, "attn_decode_joint_fwd: needs a score bound");
+  OWLK_REQUIRE(((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)o0 | (uintptr_t)o1) % 16 == 0 &&
+                   ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo0 % 8 == 0 && ldo1 % 8 == 0 && sqb % 8 == 0 &&
+                   skb % 8 == 0 && svb % 8 == 0,
+               "attn_decode_joint_fwd: q/k/v/o rows must be 16-byte aligned");
+  const long hd = (long)H * head_dim;
+  OWLK_REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo0 >= hd && ldo1 >= hd,
+               "attn_decode_joint_fwd: a row stride is shorter than its H * head_dim columns");
+  JointP p;
+  p.q = (const bf16*)q; p.k = (const bf16*)k; p.v = (const bf16*)v;
+  p.o0 = (bf16*)o0; p.o1 = (bf16*)o1; p.lse = lse;
+  p.ldq = ldq; p.sqb = sqb; p.ldk = ldk; p.skb = skb; p.ldv = ldv; p.svb = svb; p.ldo0 = ldo0; p.ldo1 = ldo1;
+  p.Lq = (long)n0 + n1; p.Lkv = Lkv; p.n0 = n0; p.n1 = n1; p.H = H;
+  p.scale_log2 = scale * LOG2E;
+  hipLaunchKernelGGL(attn_decode_joint_k, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream, p);
+  return owlk::check_launch("attn_decode_joint_fwd");
 }

@@ -460,6 +460,58 @@ __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv
   *(bf16x4*)(o + D / 2 + j * 4) = y1;
 }
 
+// MMDiT decode form (mmattn.py:46-72): the joint frames [n0 video | n1 audio] are never assembled.
+// Joint row r of frame f of batch bb is read from the video qkv GEMM output (row (bb nf + f) n0 + r,
+// r < n0) or the audio one (row (bb nf + f) n1 + r - n0); table row tab_off + f (n0 + n1) + r.  The
+// arithmetic per (token, q|k, head) row is qk_rope_fwd_k's, statement for statement, so q, k, v equal
+// frame_interleave -> qk_rope_fwd -> cache copy bit for bit.
+template <int D>
+__global__ __launch_bounds__(256) void mm_qk_rope_kv_k(const bf16* __restrict__ qkv0, long ld0,
+                                                       const bf16* __restrict__ qkv1, long ld1, long B, long nf,
+                                                       int n0, int n1, int H, const float* __restrict__ cosb,
+                                                       const float* __restrict__ sinb, long ld_tab, long tab_off,
+                                                       bf16* __restrict__ qo, long ldqo, long sqo,
+                                                       bf16* __restrict__ ko, long ldko, long sko,
+                                                       bf16* __restrict__ vo, long ldvo, long svo) {
+  constexpr int CPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long rowid = gid / CPR;  // (token, which, head)
+  const int j = gid % CPR;
+  const long tpf = n0 + n1, L = nf * tpf;
+  if (rowid >= B * L * 3 * H) return;
+  const long tok = rowid / (3 * H);
+  const int wh = rowid % (3 * H);  // which * H + head
+  const long bb = tok / L, t = tok - bb * L;
+  const long f = t / tpf, r = t - f * tpf;
+  const bf16* src = r < n0 ? qkv0 + ((bb * nf + f) * n0 + r) * ld0 : qkv1 + ((bb * nf + f) * n1 + (r - n0)) * ld1;
+  const bf16x8 v = *(const bf16x8*)(src + (long)wh * D + j * 8);
+  if (wh >= 2 * H) {  // v: copied as is
+    *(bf16x8*)(vo + bb * svo + t * ldvo + (long)(wh - 2 * H) * D + j * 8) = v;
+    return;
+  }
+  float xv[8];
+  unpack8(v, xv);
+  float ss = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ss += xv[e] * xv[e];
+#pragma unroll
+  for (int o = 1; o < CPR; o <<= 1) ss += __shfl_xor(ss, o, 64);
+  const float rr = rsqrtf(ss / D + RMS_EPS);
+  const long pos = tab_off + t;
+  const f32x4 c = *(const f32x4*)(cosb + pos * ld_tab + j * 4);
+  const f32x4 s = *(const f32x4*)(sinb + pos * ld_tab + j * 4);
+  bf16x4 y0, y1;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float x0 = rb(xv[2 * i] * rr), x1 = rb(xv[2 * i + 1] * rr);
+    y0[i] = (bf16)(x0 * c[i] - x1 * s[i]);
+    y1[i] = (bf16)(x1 * c[i] + x0 * s[i]);
+  }
+  bf16* o = wh < H ? qo + bb * sqo + t * ldqo + (long)wh * D : ko + bb * sko + t * ldko + (long)(wh - H) * D;
+  *(bf16x4*)(o + j * 4) = y0;
+  *(bf16x4*)(o + D / 2 + j * 4) = y1;
+}
+
 // backward: d(q_rot) -> inverse rotation -> rms_norm backward (recomputing xhat from raw qkv)
 template <int D>
 __global__ __launch_bounds__(256) void qk_rope_bwd_k(const bf16* __restrict__ dqk, long ldd,
@@ -932,6 +984,38 @@ static int qk_rope_kv_launch(const void* qkv, long ldq, long T, long L, int H, i
                        sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo, (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo, state,
                        n_tab, cap);
   return owlk::check_launch("qk_rope_fwd_kv");
+}
+
+extern "C" int owlk_mm_qk_rope_fwd_kv(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf, int n0,
+                                      int n1, int H, int D, const float* cosb, const float* sinb, long ld_tab,
+                                      long n_tab, long tab_off, void* qo, long ldqo, long sqo, void* ko, long ldko,
+                                      long sko, void* vo, long ldvo, long svo, void* stream) {
+  OWLK_REQUIRE(D == 64 || D == 128, "mm_qk_rope_fwd_kv: head_dim %d unsupported", D);
+  OWLK_REQUIRE(B > 0 && nf > 0 && n0 > 0 && n1 > 0 && H > 0, "mm_qk_rope_fwd_kv: bad sizes B=%ld nf=%ld n0=%d n1=%d",
+               B, nf, n0, n1);
+  const long L = nf * ((long)n0 + n1);
+  OWLK_REQUIRE(rope_rows_ok(L, n_tab, tab_off, 0), "mm_qk_rope_fwd_kv: positions %ld.. past the %ld-row rope table",
+               tab_off, n_tab);
+  OWLK_REQUIRE(ld0 >= 3L * H * D && ld1 >= 3L * H * D && ldqo >= (long)H * D && ldko >= (long)H * D &&
+                   ldvo >= (long)H * D,
+               "mm_qk_rope_fwd_kv: a row stride is shorter than its row");
+  OWLK_REQUIRE(((uintptr_t)qkv0 | (uintptr_t)qkv1) % 16 == 0 && ld0 % 8 == 0 && ld1 % 8 == 0,
+               "mm_qk_rope_fwd_kv: qkv rows must be 16-byte aligned");
+  OWLK_REQUIRE(((uintptr_t)qo | (uintptr_t)ko | (uintptr_t)vo) % 16 == 0 && ldqo % 8 == 0 && ldko % 8 == 0 &&
+                   ldvo % 8 == 0 && sqo % 8 == 0 && sko % 8 == 0 && svo % 8 == 0,
+               "mm_qk_rope_fwd_kv: destinations must be 16-byte aligned");
+  const long threads = B * L * 3 * H * (D / 8);
+  OWLK_REQUIRE(threads < (1L << 31) * 256, "mm_qk_rope_fwd_kv: too many rows for one launch");
+  dim3 g((unsigned)((threads + 255) / 256));
+  if (D == 64)
+    hipLaunchKernelGGL(mm_qk_rope_kv_k<64>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
+                       (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo,
+                       (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo);
+  else
+    hipLaunchKernelGGL(mm_qk_rope_kv_k<128>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
+                       (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo,
+                       (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo);
+  return owlk::check_launch("mm_qk_rope_fwd_kv");
 }
 
 extern "C" int owlk_qk_rope_bwd(const void* dqk, long ldd, const void* qkv, long ldq, long T, int H, int D,

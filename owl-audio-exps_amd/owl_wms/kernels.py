@@ -340,6 +340,55 @@ def attn_decode_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0, scale=Non
     return o, lse
 
 
+def mm_qk_rope_fwd_kv(qkv0, qkv1, B, nf, n0, n1, H, D, cos, sin, tab_off, q_out, k_out, v_out):
+    """MMDiT decode form: the two modalities' qkv GEMM outputs (qkv0 [B nf n0, 3 H D] video, qkv1
+    [B nf n1, 3 H D] audio) -> rotated q of the joint frames [n0 video | n1 audio] into q_out
+    [B, nf (n0 + n1), H D], rotated k into k_out and v copied into v_out (views of the KV cache's slots;
+    any row / batch strides).  The bits of frame_interleave -> qk_rope_fwd -> SingleKVCache.extend."""
+    L = nf * (n0 + n1)
+    for t, rows, nm in ((qkv0, B * nf * n0, "qkv0"), (qkv1, B * nf * n1, "qkv1")):
+        assert t.dim() == 2 and t.shape == (rows, 3 * H * D) and t.stride(1) == 1 and t.dtype == BF16, nm
+    for t, nm in ((q_out, "q_out"), (k_out, "k_out"), (v_out, "v_out")):
+        assert t.shape == (B, L, H * D) and t.stride(2) == 1 and t.dtype == BF16, nm
+    assert cos.stride(1) == 1 and sin.stride(0) == cos.stride(0) and cos.shape[1] * 2 == D
+    call("owlk_mm_qk_rope_fwd_kv", ptr(qkv0), qkv0.stride(0), ptr(qkv1), qkv1.stride(0), B, nf, n0, n1, H, D, ptr(cos),
+         ptr(sin), cos.stride(0), cos.shape[0], tab_off, ptr(q_out), q_out.stride(1), q_out.stride(0), ptr(k_out),
+         k_out.stride(1), k_out.stride(0), ptr(v_out), v_out.stride(1), v_out.stride(0), stream())
+
+
+JOINT_DECODE_ROWS = 80  # owlk_attn_decode_joint_fwd: query rows of one joint frame (five 16-row tiles)
+
+
+def decode_joint_supported(D, n0, n1):
+    """owlk_attn_decode_joint_fwd's shapes: head_dim 64, one joint frame of at most 80 rows."""
+    return D == 64 and n0 > 0 and n1 > 0 and n0 + n1 <= JOINT_DECODE_ROWS
+
+
+def attn_decode_joint_fwd(q, k, v, H, D, n0, n1, scale=None, score_bound=0.0, want_lse=False, o0=None, o1=None):
+    """One joint MMDiT frame q [B, n0 + n1, H D] against the key rows k / v [B, Lkv, H D] ([cache | new]
+    views, or a window of them), unmasked -> (o0 [B n0, H D] video rows, o1 [B n1, H D] audio rows, lse
+    [B, H, n0 + n1] base 2 or None)."""
+    _v3(q, "q"), _v3(k, "k"), _v3(v, "v")
+    B, Lq, Lkv = q.shape[0], q.shape[1], k.shape[1]
+    assert decode_joint_supported(D, n0, n1) and Lq == n0 + n1, \
+        f"attn_decode_joint_fwd: head_dim {D} / frame of {n0} + {n1} rows not supported"
+    assert k.shape[0] == B and v.shape[:2] == k.shape[:2] and Lkv > 0
+    for t in (q, k, v):
+        assert t.shape[2] >= H * D
+    if o0 is None:
+        o0 = torch.empty(B * n0, H * D, device=q.device, dtype=BF16)
+    if o1 is None:
+        o1 = torch.empty(B * n1, H * D, device=q.device, dtype=BF16)
+    _rowmajor(o0, "o0"), _rowmajor(o1, "o1")
+    assert o0.shape == (B * n0, H * D) and o1.shape == (B * n1, H * D)
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32) if want_lse else None
+    call("owlk_attn_decode_joint_fwd", ptr(q), q.stride(1), q.stride(0), ptr(k), k.stride(1), k.stride(0), ptr(v),
+         v.stride(1), v.stride(0), ptr(o0), o0.stride(0), ptr(o1), o1.stride(0), ptr(lse), B, H, n0, n1, Lkv, D,
+         float(scale if scale is not None else D ** -0.5), float(score_bound), stream(), key="attn_decode_joint",
+         flops=4.0 * D * H * B * Lq * Lkv)
+    return o0, o1, lse
+
+
 def qk_rope_bwd(dqk, qkv, rstd, H, D, cos, sin, dqkv, tab_off=0, tpos_div=0, dbias=None):
     """-> dqkv[:, :2HD]; with dbias (fp32 [2HD]) also dbias += column sums of those outputs (the q / k
     part of the qkv bias gradient), fused into the same pass where the shape allows."""

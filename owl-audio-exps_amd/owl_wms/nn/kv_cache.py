@@ -87,6 +87,15 @@ class SingleKVCache:
         self.start = [0] * self.config.n_layers
         self.len = [0] * self.config.n_layers
 
+    def rewind(self):
+        """reset() that keeps every layer's buffers: an empty cache at the same addresses (the causal
+        window samplers refill it for every generated frame; a captured HIP graph replays on it)."""
+        assert self.bufs is not None, "Must reset cache before using"
+        self.dev = None
+        self.offsets = [0] * self.config.n_layers
+        self.start = [0] * self.config.n_layers
+        self.len = [0] * self.config.n_layers
+
     def _views(self, i, n):
         kb, vb = self.bufs[i]
         s = self.start[i]

@@ -21,6 +21,10 @@ KV cache (mmattn.py:46-72, decode / sampling, no grad): the new joint frame(s) a
 offset = the layer's cached length, [cache | new] K/V are read in place (SingleKVCache.extend),
 the cache is committed when updates are enabled, and the attention keeps the frame mask with
 q_offset = the cached length (the reference's create_causal_block_mask(n_cached_tokens=offset)).
+With MMDIT.enable_decoding() (off by default; the causal audio + video samplers switch it on around
+their decode steps) a cached call at head_dim 64 takes MMDiTBlock._forward_decode: the rope kernel reads
+the two qkv outputs and writes k / v straight into the cache (no interleave, no extend copies), and one
+new frame runs the joint decode attention with the video / audio rows written apart (no split).
 """
 import torch
 from torch import nn
@@ -263,15 +267,22 @@ class MMAttn(nn.Module):
 
 
 class MMDiTBlock(nn.Module):
+    # _forward_decode's single-frame attention: the joint decode kernel (False: the masked attn_fwd +
+    # frame_split after the joint-frame rope kernel; tools/av_decode_bench.py times the two apart)
+    joint_attention = True
+
     def __init__(self, config, layer_idx, rope=None):
         super().__init__()
         self.config = config
         self.attn = MMAttn(config, layer_idx, rope)
         self.mlps = nn.ModuleList([MLP(config) for _ in range(2)])
+        self.decoding = False  # MMDIT.enable_decoding: the fused cache path (_forward_decode)
 
     def forward(self, x0, x1, cond0, cond1, block_mask=None, kv_cache=None):
         if kv_cache is not None:
             with torch.no_grad():
+                if self.decoding and self._decode_ok(block_mask, kv_cache):
+                    return self._forward_decode(x0, x1, cond0, cond1, block_mask, kv_cache)
                 return self._forward_cached(x0, x1, cond0, cond1, block_mask, kv_cache)
         cfg, a = self.config, self.attn
         H = cfg.n_heads
@@ -331,6 +342,58 @@ class MMDiTBlock(nn.Module):
         outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
         return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
 
+    def _decode_ok(self, block_mask, kv_cache):
+        """The fused decode path's cases (MMDIT.enable_decoding): head_dim 64, the causal frame mask, a
+        cache read as stored with slots to write into."""
+        cfg = self.config
+        return cfg.d_model // cfg.n_heads == 64 and block_mask is not None and block_mask.causal and \
+            block_mask.arrays is None and kv_cache.noise_caches == 0.0 and hasattr(kv_cache, "extend_slots")
+
+    def _forward_decode(self, x0, x1, cond0, cond1, block_mask, kv_cache):
+        """_forward_cached with the joint frames never assembled (MMDIT.enable_decoding): the rope kernel
+        reads the two qkv GEMM outputs and writes q, and k / v straight into the cache's slots
+        (kernels.mm_qk_rope_fwd_kv: no frame_interleave, no extend copies; the same q, k, v bit for bit).
+        One new frame then takes the joint decode attention (kernels.attn_decode_joint_fwd: unmasked over
+        the [cache | new] rows the frame mask allows -- all of them, the last `window` frames on a windowed
+        layer -- with the video / audio rows written apart, no frame_split); several frames keep the masked
+        attn_fwd and are bit-identical to _forward_cached.  14 launches per block and decode step against
+        18: AdaLN x 2, qkv GEMM x 2, rope, attention, block_tail x 2 (4 each)."""
+        cfg, a = self.config, self.attn
+        d, H = cfg.d_model, cfg.n_heads
+        D = d // H
+        n0, n1 = cfg.sample_size ** 2, 1
+        B, T0, _ = x0.shape
+        nf = T0 // n0
+        T = nf * (n0 + n1)
+        ns = (n0, n1)
+        xs = (x0.reshape(-1, d).to(BF16).contiguous(), x1.reshape(-1, d).to(BF16).contiguous())
+        ms = (cond0.reshape(B * nf, 6 * d), cond1.reshape(B * nf, 6 * d))
+        qkv = []
+        for s in range(2):
+            h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
+            wqkv, bqkv = self.qkv_params(s)
+            qkv.append(K.gemm(h, bf16_weight(wqkv), bias=bqkv))
+        li = a.layer_idx
+        offset = kv_cache.length_at(li)
+        assert block_mask.q_offset == offset and block_mask.tpf == n0 + n1, "the frame mask describes this cache"
+        q = torch.empty(B, T, d, device=x0.device, dtype=BF16)
+        ks, vs = kv_cache.extend_slots(li, T, q)
+        K.mm_qk_rope_fwd_kv(qkv[0], qkv[1], B, nf, n0, n1, H, D, a.rope.cos, a.rope.sin, offset, q, ks, vs)
+        del qkv
+        k, v = kv_cache.extended(li, T)
+        if kv_cache.should_update:
+            kv_cache.update(k, v, li)  # the rows are in place: committed without a copy
+        if nf == 1 and self.joint_attention and K.decode_joint_supported(D, n0, n1) and K.qk_norm_bound(D) > 0.0:
+            if block_mask.window:  # |frame_q - frame_kv| < window: the last `window` frames, this one included
+                w = int(block_mask.window) * (n0 + n1)
+                k, v = k[:, -w:], v[:, -w:]
+            os_ = K.attn_decode_joint_fwd(q, k, v, H, D, n0, n1, score_bound=K.qk_norm_bound(D))[:2]
+        else:
+            o, _ = K.attn_fwd(q, k, v, H, D, block_mask, score_bound=K.qk_norm_bound(D))
+            os_ = K.frame_split(o.view(B * T, d), n0, n1)
+        outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
+        return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
+
 
 class MMDIT(nn.Module):
     def __init__(self, config):
@@ -341,6 +404,19 @@ class MMDIT(nn.Module):
         self.local_layers = [(i % 4 != 0) for i in range(config.n_layers)]
         self.blocks = nn.ModuleList([MMDiTBlock(config, i, self.rope) for i in range(config.n_layers)])
         self.cond_proj = nn.Sequential(nn.SiLU(), nn.Linear(config.d_model, config.d_model * 2 * 2 * 3))
+        self.decoding = False
+
+    def enable_decoding(self):
+        """KV-cache forwards take MMDiTBlock._forward_decode where it applies (head_dim 64); off by
+        default, and with it off every cached call is _forward_cached as before."""
+        self.decoding = True
+        for b in self.blocks:
+            b.decoding = True
+
+    def disable_decoding(self):
+        self.decoding = False
+        for b in self.blocks:
+            b.decoding = False
 
     def get_block_mask(self, x0, x1, kv_cache, window_len):
         """mmattn.py:132-143: causal frame mask over [cache | new] (q_offset = cached tokens)."""

@@ -1,9 +1,15 @@
 """Samplers (reference: owl_wms/sampling/__init__.py:1-39).
 
 Implemented on libowlk's KV-cache decode path: ``av_caching`` (AVCachingSamplerV2, the registry
-entry the reference resolves it to) and ``audio_caching``.  The window / causal-window samplers
-and the one-step variant are outside this build's hot-path scope.
+entry the reference resolves it to), ``audio_caching``, and the audio + video core's samplers
+``av_window`` / ``av_causal`` / ``av_causal_no_cfg`` (av_window.py; the causal ones decode on the
+MMDiT's fused joint-frame path).  The one-step variant is outside this build's scope (SURVEY.md
+§8(f); the reference's import of it is broken).
 """
+
+# the samplers that take the (video, audio) core: sampler(model, video, audio, mouse, btn)
+AV_WINDOW_SAMPLERS = {"av_window": "AVWindowSampler", "av_causal": "CausalAVWindowSampler",
+                      "av_causal_no_cfg": "CausalAVWindowSamplerNoCFG"}
 
 
 def get_sampler_cls(sampler_id):
@@ -13,6 +19,9 @@ def get_sampler_cls(sampler_id):
     if sampler_id == "audio_caching":
         from .audio_caching import AudioCachingSampler
         return AudioCachingSampler
-    if sampler_id in ("av_window", "av_causal", "av_causal_no_cfg", "av_caching_one_step"):
+    if sampler_id in AV_WINDOW_SAMPLERS:
+        from . import av_window
+        return getattr(av_window, AV_WINDOW_SAMPLERS[sampler_id])
+    if sampler_id == "av_caching_one_step":
         raise NotImplementedError(f"sampler {sampler_id!r} is out of scope for the MI355X build (SURVEY.md §8(f))")
     raise ValueError(f"unknown sampler_id {sampler_id!r}")

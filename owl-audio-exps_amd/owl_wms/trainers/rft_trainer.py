@@ -22,7 +22,7 @@ import torch.distributed as dist
 from ..data import get_loader
 from ..models import get_model_cls
 from ..muon import FusedAdamW, init_muon
-from ..sampling import get_sampler_cls
+from ..sampling import AV_WINDOW_SAMPLERS, get_sampler_cls
 from ..schedulers import get_scheduler_cls
 from ..utils import Timer, batch_permute_to_length, strip_prefixes
 from ..utils.grad_reducer import EMA, GradReducer
@@ -241,4 +241,34 @@ class AVRFTTrainer(RFTTrainer):
         return loss
 
     def eval_setup(self):
-        return None, None
+        """av_trainer.py:208-221: the samplers that take the (video, audio) core; any other sampler_id
+        (or none) samples nothing."""
+        if self.train_cfg.get("sampler_id") not in AV_WINDOW_SAMPLERS:
+            return None, None
+        return super().eval_setup()
+
+    @torch.no_grad()
+    def eval_step(self, sample_loader, sampler):
+        """LatentEval.eval_step for the (video, audio) samplers: the EMA core on one sample batch with
+        synthetic audio latents (as batch_loss), summary statistics of both modalities' latents."""
+        ema_core = self.eval_core()
+        vid, mouse, btn = [x.cuda() for x in next(sample_loader)[:3]]
+        g = torch.Generator().manual_seed(len(self.history))
+        audio = torch.randn(vid.shape[0], vid.shape[1], self.model_cfg.audio_channels, generator=g).cuda().to(vid.dtype)
+        vid = vid / self.train_cfg.vae_scale
+        n_ctx = vid.size(1)
+        latent, audio_out = sampler(ema_core, vid, audio, mouse, btn)[-4:-2]
+        if self.sampler_only_return_generated:
+            latent, audio_out = latent[:, n_ctx:], audio_out[:, n_ctx:]
+        out = {"eval/samples": latent.shape[0] * self.world_size, "eval/frames": latent.shape[1],
+               "eval/latent_std": latent.float().std().item(), "eval/audio_std": audio_out.float().std().item()}
+        if self.train_cfg.get("eval_sample_dir"):
+            full = self._gather_concat_cpu(latent)
+            full_a = self._gather_concat_cpu(audio_out)
+            if self.rank == 0:
+                d = Path(self.train_cfg.eval_sample_dir)
+                d.mkdir(parents=True, exist_ok=True)
+                torch.save(full, d / f"vid.{self.total_step_counter}.pt")
+                torch.save(full_a, d / f"audio.{self.total_step_counter}.pt")
+        self.barrier()
+        return out if self.rank == 0 else None
