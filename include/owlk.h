@@ -96,6 +96,12 @@ long owlk_gemm_ws_bytes(long M, long N, long K, long batch, int a_trans, int b_t
  * OWLK_DECODE_COUNTER_BYTES; every launch leaves them zero); 0 when the plan keeps no state in ws */
 long owlk_gemm_ws_counter_bytes(long M, long N, long K, long batch, int a_trans, int b_trans, int c_f32, int epi,
                                 float beta);
+/* Body of the 256^2-tile GEMMs, process-wide: 2 = ping-pong kernel with the generated, hand-placed K-loop
+ * (default), 1 = the same kernel with its HIP-source K-loop, 0 = the plain 256^2 kernel; -1 = back to the
+ * default / the environment (OWLK_GEMM_PP, read once).  All three give the same bits.  min_tiles >= 0
+ * replaces the fewest 256^2 tiles a GEMM needs to take these kernels (default 192, OWLK_GEMM_MIN256), so a
+ * small test shape reaches them; -1 restores it.  For A/B runs and tests, not for the training step. */
+int owlk_set_gemm_pp(int body, long min_tiles);
 
 /* ---- AdaLN modulate (modulation.py:7-26 AdaLN.forward after its fc; :46-55 cond_adaln):
  *   y[t] = bf16(bf16(bf16(rms_norm(x[t])) * bf16(1 + scale[t/tpf])) + shift[t/tpf]); rstd[t] fp32 */

@@ -779,11 +779,46 @@ __global__ __launch_bounds__(NT8, 1) void gemm256_kernel(GemmP p) {
 // its previous contents (B last read in phase 1, A in phase 2, group 1 one barrier later).
 // RAW: every wave's vmcnt for tile t+1 precedes (in barrier order) the first read of it.
 // FS: frame-strided rows (GemmP::a_fs / b_fs / c_fs) of A (bit 0), B (bit 1), C (bit 2; bf16 STORE)
-template <bool AT, bool BT, int EPI, bool OF32, int FS = 0>
+// ASM: the K-loop is the generated, hand-placed statement of gemm_pp_step.inc (gemm_pp_loop: same
+// tile, waves, LDS images, phases and K order -- bitwise the same accumulators -- on a ring of ten
+// half-tile slots, one half-tile staged per phase; tools/gen_gemm_pp_asm.py).  Plain rows only (FS = 0).
+#include "gemm_pp_step.inc"
+
+// the lane operands of gemm_pp_loop: glds_tile's source chunk and read_frag_async's LDS address, as
+// offsets from the tile's first K-tile (ab / bb) and from K-tile 0's ring slots
+template <bool TRANS>
+DEV unsigned ppa_dma_off(long ld, long rel0, long lim, int wave, int lane, int i) {
+  if (!TRANS) {
+    const int row = (wave * 2 + i) * 8 + (lane >> 3);
+    const int ch = (lane & 7) ^ ((row >> 1) & 7);
+    long rel = rel0 + row;
+    rel = rel < lim ? rel : lim;  // ragged last tile: rows clamped (k-contiguous operands only)
+    return (unsigned)(rel * ld * 2 + ch * 16);
+  }
+  const int k = (wave * 2 + i) * 4 + lane / 16;
+  const int pch = lane % 16;
+  const int lch = (((pch >> 1) ^ swz_t<128>(k)) << 1) | (pch & 1);
+  return (unsigned)(((long)k * ld + rel0 + lch * 8) * 2);
+}
+// x: k-substep (k-contiguous) or the 16-row block inside the wave's half-tile (transposed); row0: the
+// wave's first row inside the half-tile for k-contiguous operands (a multiple of 16)
+template <bool TRANS>
+DEV unsigned ppa_read_addr(unsigned base, int x, int row0, int lane) {
+  if (!TRANS) {
+    const int r = lane & 15, kc = 4 * x + (lane >> 4);
+    return base + (row0 + r) * 128 + ((kc ^ ((r >> 1) & 7)) << 4);
+  }
+  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
+  const int k0 = 8 * g + q;
+  return base + k0 * 256 + ((x ^ swz_t<128>(k0)) << 5) + pp * 8;
+}
+
+template <bool AT, bool BT, int EPI, bool OF32, int FS = 0, bool ASM = false>
 __global__ __launch_bounds__(NT8, 1) void gemm_pp_kernel(GemmP p) {
   constexpr bool FA = FS & 1, FB = (FS & 2) != 0, FC = (FS & 4) != 0;
   constexpr int HALF = 128 * BK * 2, STAGE = 4 * HALF;
-  __shared__ __attribute__((aligned(16))) char smem[2 * STAGE];
+  static_assert(!ASM || FS == 0, "the generated K-loop reads plain rows");
+  __shared__ __attribute__((aligned(16))) char smem[ASM ? PPA_LDS_BYTES : 2 * STAGE];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wr = wave >> 2, wc = wave & 3;
 
@@ -819,6 +854,47 @@ __global__ __launch_bounds__(NT8, 1) void gemm_pp_kernel(GemmP p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+  if constexpr (ASM) {
+    f32x16 cv[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) cv[i][e] = 0.f;
+    const unsigned L0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
+    PPLane f;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        f.dma[2 * h + i] = ppa_dma_off<BT>(p.ldb, 128 * h, p.N - 1 - n0, wave, lane, i);
+        f.dma[4 + 2 * h + i] = ppa_dma_off<AT>(p.lda, 128 * h, p.M - 1 - m0, wave, lane, i);
+      }
+    const unsigned abase = L0 + PPA_A_PAIR0 + wr * HALF, bbase = L0 + (wc >> 1) * HALF;
+#pragma unroll
+    for (int x = 0; x < 8; ++x) f.ra[x] = ppa_read_addr<AT>(abase, x, 0, lane);
+#pragma unroll
+    for (int x = 0; x < 4; ++x) f.rb[x] = ppa_read_addr<BT>(bbase, BT ? 4 * (wc & 1) + x : x, (wc & 1) * 64, lane);
+    const bf16* ab = AT ? A + kbeg * p.lda + m0 : A + m0 * p.lda + kbeg;
+    const bf16* bb = BT ? B + kbeg * p.ldb + n0 : B + n0 * p.ldb + kbeg;
+    // wave-uniform by construction; readfirstlane so that hipcc keeps them in SGPRs
+    auto sgpr = [](unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); };
+    auto sptr = [&](const bf16* q) {
+      const unsigned long long u = (unsigned long long)q;
+      return (const void*)((unsigned long long)sgpr((unsigned)u) | ((unsigned long long)sgpr((unsigned)(u >> 32)) << 32));
+    };
+    u32x4 sc;
+    sc[0] = sgpr(AT ? (unsigned)(BK * p.lda * 2) : BK * 2);
+    sc[1] = sgpr(BT ? (unsigned)(BK * p.ldb * 2) : BK * 2);
+    sc[2] = sgpr(L0 + (unsigned)(wave * 2048));
+    sc[3] = sgpr((unsigned)wr);
+    gemm_pp_loop<AT, BT>(cv, f, sptr(ab), sptr(bb), sgpr((unsigned)nk), sc);
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[i][j][r] = cv[i][4 * j + r];
+  } else {  // ---- the HIP-source K-loop (its lines keep their indentation)
   auto issueA = [&](int t) {
     char* st = smem + (t & 1) * STAGE;
     glds_tile<128, AT, FA>(st, A, p.lda, m0, kbeg + (long)t * BK, p.M, wave, lane, p.a_fs);
@@ -907,6 +983,7 @@ __global__ __launch_bounds__(NT8, 1) void gemm_pp_kernel(GemmP p) {
   if (wr == 0) OWLK_PP_BAR();  // pairs with group 1's final barrier: every MFMA / LDS read done
 #undef OWLK_PP_BAR
 #undef OWLK_PP_SYNC
+  }
 #ifdef OWLK_GEMM_EXP_NOEPI  // timing experiment only (tools/build_variant.sh -DOWLK_GEMM_EXP_NOEPI)
   {
     float t = 0.f;
@@ -1149,13 +1226,23 @@ int dispatch_e(GemmP& p, int at, int bt, int epi, int cf32, long batch, hipStrea
 }
 
 
+// Body of the 256^2 GEMMs: 2 = gemm_pp_kernel with the generated K-loop (default), 1 = gemm_pp_kernel's
+// HIP-source loop, 0 = gemm256_kernel.  OWLK_GEMM_PP is read once; owlk_set_gemm_pp overrides it (and
+// the fewest 256^2 tiles that take these kernels) for the whole process.
+int g_pp_body = -1;
+long g_min_tiles256 = -1;
+int pp_body() {
+  static const int env = getenv("OWLK_GEMM_PP") ? atoi(getenv("OWLK_GEMM_PP")) : 2;
+  return g_pp_body >= 0 ? g_pp_body : env;
+}
+
 template <bool AT, bool BT, int EPI, bool OF32>
 int launch256(GemmP& p, long batch, hipStream_t s) {
   p.tiles_m = (int)((p.M + 255) / 256);
   p.tiles_n = (int)((p.N + 255) / 256);
   const int splits = (int)((p.K + p.kchunk - 1) / p.kchunk);
   dim3 grid(p.tiles_m * p.tiles_n, (unsigned)splits, (unsigned)batch);
-  static const int pp = getenv("OWLK_GEMM_PP") ? atoi(getenv("OWLK_GEMM_PP")) : 1;
+  const int pp = pp_body();
   static const int fuse_cs = getenv("OWLK_GEMM_COLSUM") ? atoi(getenv("OWLK_GEMM_COLSUM")) : 1;
   if (pp && EPI == EPI_DSILU && batch == 1 && fuse_cs) p.colsum = p.colsum_req;
   // grouped tile order for the short-K GEMMs (K <= 4096: -2..4 % at dit_v4's K = 1536 shapes, -2..6 %
@@ -1204,7 +1291,12 @@ int launch256(GemmP& p, long batch, hipStream_t s) {
   }
   if constexpr (EPI == EPI_DELTA || EPI == EPI_QKROPE) {
     OWLK_REQUIRE(pp && splits == 1 && batch == 1, "gemm: the delta / rope epilogues run in the unsplit ping-pong kernel");
-    hipLaunchKernelGGL((gemm_pp_kernel<AT, BT, EPI, OF32>), grid, dim3(NT8), 0, s, p);
+    if (pp >= 2)
+      hipLaunchKernelGGL((gemm_pp_kernel<AT, BT, EPI, OF32, 0, true>), grid, dim3(NT8), 0, s, p);
+    else
+      hipLaunchKernelGGL((gemm_pp_kernel<AT, BT, EPI, OF32>), grid, dim3(NT8), 0, s, p);
+  } else if (pp >= 2) {
+    hipLaunchKernelGGL((gemm_pp_kernel<AT, BT, EPI, OF32, 0, true>), grid, dim3(NT8), 0, s, p);
   } else if (pp) {
     hipLaunchKernelGGL((gemm_pp_kernel<AT, BT, EPI, OF32>), grid, dim3(NT8), 0, s, p);
   } else {
@@ -1514,7 +1606,13 @@ static bool fits256(long M, long N, long K, int a_trans, int b_trans, int c_f32,
 // 128^2 kernel: the per-frame modulation GEMM [1,536 x 9,216 x 1,536] has 216); OWLK_GEMM_MIN256 for A/B
 static long min_tiles256() {
   static const long v = getenv("OWLK_GEMM_MIN256") ? atol(getenv("OWLK_GEMM_MIN256")) : 192;
-  return v;
+  return g_min_tiles256 >= 0 ? g_min_tiles256 : v;
+}
+extern "C" int owlk_set_gemm_pp(int body, long min_tiles) {
+  OWLK_REQUIRE(body >= -1 && body <= 2, "owlk_set_gemm_pp: body %d (0 gemm256, 1 ping-pong, 2 generated loop, -1 default)", body);
+  g_pp_body = body;
+  g_min_tiles256 = min_tiles < 0 ? -1 : min_tiles;
+  return 0;
 }
 // Skinny-M GEMMs (decode: one 64-token frame against the full weights) give few 64x64 tiles; split K
 // so the grid streams the weights from every CU: bf16 output with STORE (beta 0) / SILU / GATE_RESID
@@ -1788,7 +1886,7 @@ extern "C" int owlk_gemm_attn_delta(long M, long N, long K, const void* dY, long
                                     float* delta, void* stream) {
   OWLK_REQUIRE(L > 0 && M % L == 0 && H > 0 && D > 0 && N == (long)H * D && o && delta,
                "gemm_attn_delta: bad shape M=%ld N=%ld L=%ld H=%d D=%d", M, N, L, H, D);
-  static const int pp = getenv("OWLK_GEMM_PP") ? atoi(getenv("OWLK_GEMM_PP")) : 1;
+  const int pp = pp_body();
   static const int fuse_env = getenv("OWLK_GEMM_DELTA") ? atoi(getenv("OWLK_GEMM_DELTA")) : 1;
   const long tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
   const SplitPlan pl = split_plan(M, N, K, 1, 0, 1, 0, EPI_DELTA, 0.f);
@@ -1825,7 +1923,7 @@ extern "C" int owlk_gemm_qk_rope(long M, long N, long K, const void* A, long lda
     OWLK_REQUIRE(n_tab > 0 && tab_off >= 0 && tab_off + span <= n_tab,
                  "gemm_qk_rope: positions %ld.. past the %ld-row rope table", tab_off, n_tab);
   }
-  static const int pp = getenv("OWLK_GEMM_PP") ? atoi(getenv("OWLK_GEMM_PP")) : 1;
+  const int pp = pp_body();
   static const int fuse_env = getenv("OWLK_GEMM_ROPE") ? atoi(getenv("OWLK_GEMM_ROPE")) : 1;
   const long tiles256 = ((M + 255) / 256) * ((N + 255) / 256);
   const SplitPlan pl = split_plan(M, N, K, 1, 0, 0, 0, EPI_QKROPE, 0.f);

@@ -671,6 +671,7 @@ def emit_helpers():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--out", default=OUT, help="write the generated file here")
     args = ap.parse_args()
     parts = []
     for kind in ("full", "masked", "empty"):
@@ -717,9 +718,9 @@ def main():
            "  unsigned m0a, m0f, m0q, m0l;\n"
            "  const void *qb, *ob, *lb, *fb;\n"
            "};\n\n")
-    with open(OUT, "w") as f:
+    with open(args.out, "w") as f:
         f.write(hdr + emit_helpers() + "\n" + "\n".join(parts) + "\n" + "\n".join(disp))
-    print("wrote", OUT, file=sys.stderr)
+    print("wrote", args.out, file=sys.stderr)
 
 
 if __name__ == "__main__":

@@ -455,6 +455,7 @@ def emit_helpers():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--out", default=OUT, help="write the generated file here")
     args = ap.parse_args()
     self_check()
     parts = []
@@ -488,9 +489,9 @@ def main():
            "struct W4Lane {\n  unsigned kr[2], vt[4], ko[2], vo[2];\n  int mlo[8], mhi[8];\n};\n"
            "// wave-uniform: M0 base of this wave's DMA rows, the DMA sources (K / V tile t + 2)\n"
            "struct W4Scalar {\n  unsigned m0k;\n  const void *kb, *vb;\n};\n\n")
-    with open(OUT, "w") as f:
+    with open(args.out, "w") as f:
         f.write(hdr + emit_helpers() + "\n" + "\n".join(parts) + "\n" + "\n".join(disp))
-    print("wrote", OUT, file=sys.stderr)
+    print("wrote", args.out, file=sys.stderr)
 
 
 if __name__ == "__main__":

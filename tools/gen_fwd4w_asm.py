@@ -416,6 +416,7 @@ def emit_helpers():
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--stats", action="store_true")
+    ap.add_argument("--out", default=OUT, help="write the generated file here")
     args = ap.parse_args()
     self_check()
     parts = [emit_tile(slot, masked) for masked in (False, True) for slot in range(NSLOT)]
@@ -444,9 +445,9 @@ def main():
            "// relative to the tile and to the lane's 4 h rows\n"
            "struct W4Lane {\n  unsigned kr[4], vt[2], ko[2], vo[2];\n  int mlo[4], mhi[4];\n};\n"
            "struct W4Scalar {\n  unsigned m0k;\n  const void *kb, *vb;\n};\n\n")
-    with open(OUT, "w") as f:
+    with open(args.out, "w") as f:
         f.write(hdr + emit_helpers() + "\n" + "\n".join(parts) + "\n" + "\n".join(disp))
-    print("wrote", OUT, file=sys.stderr)
+    print("wrote", args.out, file=sys.stderr)
 
 
 if __name__ == "__main__":
