@@ -423,6 +423,25 @@ int owlk_adamw(int count, float* const* p, const float* const* g, float* const* 
  * `count` fp32 tensors of n[i] elements, torch's lerp formula (weight = 1 - decay). */
 int owlk_ema(int count, float* const* shadow, const float* const* p, const long* n, float weight, void* stream);
 
+/* ---- gradient guard (grad_guard.hip): the global L2 norm of `count` fp32 buffers of n[i] >= 0 elements
+ * (host arrays; device pointers 16-B aligned), whether it is finite, and the fused norm clip.  The
+ * reference clips and lets GradScaler.step skip the optimizer step on an inf / NaN gradient
+ * (sf_vid_only.py:503-508); its RFT trainers clip (rft_trainer.py:197-199).
+ *   state: device float[4] (16-B aligned) = {total_norm, clip_coef, finite, 0}; finite = 1 iff the sum of
+ *     squares is finite (a NaN / Inf element or an fp32 overflow of a workgroup's partial sum clears it);
+ *     clip_coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 (torch's clip_grad_norm_), 1 when
+ *     max_norm <= 0 (norm only) or the sum is not finite.
+ *   With max_norm > 0 the buffers are scaled by clip_coef in place when it is < 1, and left bit for bit
+ *   otherwise.  Workgroup i of a buffer sums its elements [i * 65536, (i + 1) * 65536) in fp32, one wave adds
+ *   the partials in index order in double: the result depends on (count, n[], values) alone, never on
+ *   the CU count or owlk_set_cu_reserve.  No host synchronisation; buffers beyond OWLK_GRAD_GUARD_TABLE go
+ *   in further launches.  ws: owlk_grad_guard_ws_bytes(count, n) bytes (0 for a bad argument or no elements),
+ *   4-B aligned. */
+#define OWLK_GRAD_GUARD_TABLE 16
+long owlk_grad_guard_ws_bytes(int count, const long* n);
+int owlk_grad_guard(int count, float* const* g, const long* n, float max_norm, float* state, void* ws,
+                    long ws_bytes, void* stream);
+
 /* ---- MMDiT plumbing (frames.hip) ----
  * owlk_frame_mux replaces the per-frame concat / split of mmattn.py:54-60 and :77-80: frame f of
  * the joint sequence is [n0 rows of a (video) | n1 rows of b (audio)].  dir 0: a, b -> joint;

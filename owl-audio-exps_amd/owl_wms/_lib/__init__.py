@@ -82,6 +82,8 @@ _SIGS = {
     "owlk_muon_apply": [I, P, P, L, L, I, F, F, P],
     "owlk_adamw": [I, P, P, P, P, P, F, F, F, F, F, F, F, P],
     "owlk_ema": [I, P, P, P, F, P],
+    "owlk_grad_guard_ws_bytes": [I, P],
+    "owlk_grad_guard": [I, P, P, F, P, P, L, P],
 }
 
 # size queries; every other entry returns an int status
@@ -90,7 +92,7 @@ _RESTYPES = {n: ctypes.c_long for n in ("owlk_gemm_splitk_bytes", "owlk_gemm_ws_
                                         "owlk_attn_decode_bwd_ws_bytes",
                                         "owlk_dmd_loss_ws_bytes", "owlk_critic_loss_ws_bytes",
                                         "owlk_colsum_ws_bytes", "owlk_ns_iterate_ws_bytes",
-                                        "owlk_newton_schulz_ws_bytes")}
+                                        "owlk_newton_schulz_ws_bytes", "owlk_grad_guard_ws_bytes")}
 
 _lib = None
 

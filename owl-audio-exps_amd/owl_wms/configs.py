@@ -72,6 +72,9 @@ class TrainingConfig:
     update_ratio: int = 5  # critic updates per student update (every reference distillation config)
     rollout_steps: int = 1  # RolloutManager's defaults (sf_vid_only.py:113)
     min_rollout_frames: int = 8
+    grad_guard: bool = False  # skip the optimizer step on a non-finite gradient; fused norm + clip
+    grad_clip_norm: float = 10.0  # the non-Muon clip threshold (every reference trainer but mixed_av: 10)
+    max_consecutive_skips: int = None  # with grad_guard: raise after more than this many skips in a row
     sample_interval: int = 1000
     save_interval: int = 1000
     n_samples: int = 8

@@ -945,6 +945,43 @@ def ema_lerp(shadow, params, weight):
     _written(shadow)
 
 
+GRAD_GUARD_TABLE = 16  # OWLK_GRAD_GUARD_TABLE: buffers per launch of the gradient guard
+_grad_guard_ws = {}  # (device, lengths) -> workspace of per-workgroup partial sums
+
+
+def grad_guard(bufs, max_norm=None):
+    """owlk_grad_guard over fp32 contiguous device buffers (the reducer's flat buckets) -> state, a device fp32
+    tensor of 4: [total L2 norm, clip_coef, finite (1.0 / 0.0), 0].  ``max_norm`` None or <= 0: norm only.
+    Otherwise the buffers are scaled in place by clip_coef = min(1, max_norm / (norm + 1e-6)) when that is
+    < 1 and the norm is finite, and stay bit for bit when not.  Nothing is read back on the host."""
+    import ctypes
+    bufs = list(bufs)
+    for i, t in enumerate(bufs):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise RuntimeError(f"grad_guard: buffer {i} must be a device tensor")
+        if t.dtype != F32:
+            raise RuntimeError(f"grad_guard: buffer {i} must be float32 (got {t.dtype})")
+        if not t.is_contiguous():
+            raise RuntimeError(f"grad_guard: buffer {i} must be contiguous")
+        if t.device != bufs[0].device:
+            raise RuntimeError(f"grad_guard: buffer {i} is on {t.device}, buffer 0 on {bufs[0].device}")
+        if t.data_ptr() % 16:
+            raise RuntimeError(f"grad_guard: buffer {i} must be 16-byte aligned")
+    dev = bufs[0].device if bufs else torch.device("cuda", torch.cuda.current_device())
+    ns = tuple(t.numel() for t in bufs)
+    n_arr = (ctypes.c_long * len(ns))(*ns)
+    nws = lib().owlk_grad_guard_ws_bytes(len(ns), n_arr)
+    ws = _grad_guard_ws.get((dev, ns))
+    if ws is None:
+        ws = _grad_guard_ws[(dev, ns)] = torch.empty(max(nws, 4) // 4, device=dev, dtype=F32)
+    state = torch.empty(4, device=dev, dtype=F32)
+    call("owlk_grad_guard", len(ns), _ptr_array(bufs), n_arr, float(max_norm or 0.0), ptr(state), ptr(ws), nws,
+         stream())
+    if max_norm is not None and max_norm > 0:
+        _written(bufs)
+    return state
+
+
 # ---------------------------------------------------------------- MMDiT plumbing (frames.hip)
 def frame_interleave(a, b, n0, n1, out=None):
     """a [F*n0, C], b [F*n1, C] token-major -> joint [F*(n0+n1), C] (frame f = a-rows | b-rows)."""

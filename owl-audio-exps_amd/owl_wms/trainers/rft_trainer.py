@@ -1,9 +1,9 @@
 """RFTTrainer (reference: owl_wms/trainers/rft_trainer.py:25-280) for MI355X.
 
 Step semantics kept: accum = target_batch_size // batch_size // world_size micro-steps of
-``loss / accum`` backward; then (non-Muon only) clip_grad_norm 10, optimizer step, zero grads,
-scheduler step, EMA update; logging through LogHelper (the logged ``diffusion_loss`` is the sum of
-the micro-steps' ``loss / accum``, averaged over ranks, utils/logging.py:33-64); the eval sampler
+``loss / accum`` backward; then (non-Muon only) clip_grad_norm ``train.grad_clip_norm`` (10), optimizer
+step, zero grads, scheduler step, EMA update; logging through LogHelper (the logged ``diffusion_loss`` is
+the sum of the micro-steps' ``loss / accum``, averaged over ranks, utils/logging.py:33-64); the eval sampler
 at every ``sample_interval`` (step 0 included, :213, :243-280); save every ``save_interval``.
 
 Differences (MI355X-first): no torch.compile/DDP wrapper -- the block kernels are libowlk and the
@@ -11,7 +11,10 @@ all-reduce is GradReducer (bucket views, one RCCL all-reduce per bucket on the l
 overlapped with backward); metrics go to stdout instead of wandb, and eval returns summary
 statistics of the sampled latents (no VAE decode or media: out of scope).  Optional
 ``train.seed`` seeds torch's RNG per micro-step (the reference seeds nothing),
-which makes a resumed run bit-identical to an uninterrupted one.
+which makes a resumed run bit-identical to an uninterrupted one.  Optional ``train.grad_guard``: the
+norm, the clip and a finite check in one pass over the reducer's buckets (BaseTrainer.guarded_step); a
+non-finite gradient skips the optimizer step, not the zeroing, the scheduler or the EMA (what GradScaler.step
+does in the reference's distillation trainers), and the step's record gains ``grad_norm`` and ``skipped``.
 """
 import gc
 from pathlib import Path
@@ -189,14 +192,22 @@ class RFTTrainer(LatentEval, BaseTrainer):
                 local_step += 1
                 if local_step % accum != 0:
                     continue
-                if self.train_cfg.opt.lower() != "muon":
-                    torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=10.0)
-                self.opt.step()
+                muon = self.train_cfg.opt.lower() == "muon"
+                guard = None
+                if self.train_cfg.get("grad_guard"):  # norm only for Muon: the reference never clips it
+                    guard = self.guarded_step(self.opt, self.reducer,
+                                              None if muon else self.train_cfg.grad_clip_norm)
+                else:
+                    if not muon:
+                        torch.nn.utils.clip_grad_norm_(self.model.parameters(), max_norm=self.train_cfg.grad_clip_norm)
+                    self.opt.step()
                 self.reducer.zero_grad()
                 if self.scheduler is not None:
                     self.scheduler.step()
                 self.ema.update()
                 rec = metrics.pop()
+                if guard is not None:
+                    rec["grad_norm"], rec["skipped"] = guard.norm, self.skipped
                 rec["time"] = timer.hit()
                 timer.reset()
                 if sampler is not None and self.total_step_counter % self.train_cfg.sample_interval == 0:

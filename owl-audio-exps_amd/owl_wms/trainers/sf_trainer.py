@@ -3,10 +3,11 @@ MI355X: self-forcing distillation of a causal student from a frozen teacher, wit
 the flow of the student's own rollouts (trainers/self_forcing.py has the rollout and the two losses).
 
 One outer step, as in the reference: ``update_ratio`` critic updates (student frozen), each ``accum``
-micro-steps of ``get_critic_loss / accum``, clip-norm 10 and an optimizer step; then one student update
-(critic frozen) of ``accum`` micro-steps of ``get_dmd_loss(cfg_scale=1.5) / accum``, clip-norm 10 and a
-step; then the EMA update, logging, the eval sampler every ``sample_interval`` (RFTTrainer's eval path,
-on the EMA core) and a checkpoint every ``save_interval``.  ``max_steps`` counts outer steps.
+micro-steps of ``get_critic_loss / accum``, clip-norm ``train.grad_clip_norm`` (10) and an optimizer step;
+then one student update (critic frozen) of ``accum`` micro-steps of ``get_dmd_loss(cfg_scale=1.5) / accum``,
+the same clip and a step; then the EMA update, logging, the eval sampler every ``sample_interval``
+(RFTTrainer's eval path, on the EMA core) and a checkpoint every ``save_interval``.  ``max_steps`` counts
+outer steps.
 
 Differences from the reference, on purpose:
 * RolloutManager gets ``min_rollout_frames`` and ``rollout_steps`` by keyword; the reference passes them
@@ -14,7 +15,10 @@ Differences from the reference, on purpose:
 * the student's optimizer steps once per accumulation window, like the critic's; in the reference the
   step sits inside the micro-step loop (:563), so only the last micro-step's gradient is whole;
 * no GradScaler (gradients are fp32 buckets, utils/grad_reducer.py) and no autocast (the cores run
-  their own bf16 kernels); ``load`` ignores a reference checkpoint's ``scaler`` / ``critic_scaler``;
+  their own bf16 kernels); ``load`` ignores a reference checkpoint's ``scaler`` / ``critic_scaler``.  What
+  went with the scaler, the skipped optimizer step on an inf / NaN gradient (sf_vid_only.py:503-508), is back
+  behind ``train.grad_guard``: norm, clip and finite check in one pass over the buckets, a non-finite
+  critic or student gradient skips that optimizer step only (BaseTrainer.guarded_step); off by default;
 * no DDP wrapper (GradReducer, one per trained model), no VAE decoder, no wandb: metrics go to
   ``self.history`` and stdout, eval returns summary statistics of the sampled latents (DESIGN.md §7);
 * a ``None`` checkpoint path leaves the module's own initialisation (plumbing runs and tests); a
@@ -183,8 +187,12 @@ class SelfForceTrainer(LatentEval, BaseTrainer):
         return vid / self.train_cfg.vae_scale, mouse, btn
 
     def _step(self, model, opt, reducer):
-        g_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=10.0)
-        opt.step()
+        if self.train_cfg.get("grad_guard"):
+            g_norm = self.guarded_step(opt, reducer, self.train_cfg.grad_clip_norm,
+                                       name="critic" if model is self.critic else "student").norm
+        else:
+            g_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=self.train_cfg.grad_clip_norm)
+            opt.step()
         reducer.zero_grad()
         return g_norm
 
@@ -230,6 +238,8 @@ class SelfForceTrainer(LatentEval, BaseTrainer):
         while self.max_steps is None or len(self.history) < self.max_steps:
             self.outer_step()
             rec = self.metrics.pop()
+            if self.train_cfg.get("grad_guard"):
+                rec["skipped"] = self.skipped
             rec["time"] = timer.hit()
             timer.reset()
             if sampler is not None and self.total_step_counter % self.train_cfg.sample_interval == 0:

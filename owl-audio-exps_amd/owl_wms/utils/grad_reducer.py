@@ -16,6 +16,8 @@
   the reducer asks libowlk, from its first bucket launch on, to leave ``reserve_cus`` CUs free
   (``owlk_set_cu_reserve``; default 32 = four per XCD, env ``OWL_RCCL_RESERVE_CUS``) and restores the
   full grid in ``finish()``.
+* ``grad_guard()`` after the window's last ``finish()``: the global gradient norm, a finite flag and the
+  norm clip in one deterministic libowlk pass over the flat buckets (``train.grad_guard``).
 """
 import os
 
@@ -141,6 +143,41 @@ class GradReducer:
         from .. import _lib
         _lib.call("owlk_set_cu_reserve", cus)
         self._reserved = cus > 0
+
+    def grad_guard(self, max_norm=None):
+        """One pass over the buckets after the window's last ``finish()`` (owlk_grad_guard): the global
+        gradient norm, whether it is finite, and with ``max_norm`` > 0 the norm clip in place.  ->
+        GuardResult.  With several ranks the finite flag alone is MIN-all-reduced, here and not on first
+        read, so that every rank takes the same branch whoever looks at the result: a rank that skipped
+        its optimizer step alone would leave the others waiting in Muon's all-gather."""
+        from .. import kernels as K
+        state = K.grad_guard(self.flat, max_norm)
+        if self.ws > 1:
+            dist.all_reduce(state[2:3], op=dist.ReduceOp.MIN, group=self.pg)
+        return GuardResult(state)
+
+
+class GuardResult:
+    """The device state of one gradient guard, [norm, clip_coef, finite, 0]; ``norm`` and ``finite``
+    read it in one device-to-host copy on first access (the one synchronisation per optimizer
+    step that the reference's GradScaler.step makes too)."""
+
+    def __init__(self, state):
+        self.state = state
+        self._host = None
+
+    def _read(self):
+        if self._host is None:
+            self._host = self.state.tolist()
+        return self._host
+
+    @property
+    def norm(self):
+        return self._read()[0]
+
+    @property
+    def finite(self):
+        return self._read()[2] != 0.0
 
 
 class EMA:
