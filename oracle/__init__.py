@@ -7,7 +7,9 @@ HIP library is missing.
 
 Parity status: PINNED.  ``tests/test_oracle_golden.py`` checks every function here against the
 golden vectors in ``tests/golden/`` which were produced by importing the reference package
-itself on CPU (``tests/golden/make_golden.py``, SURVEY.md §8(c) recipe).
+itself on CPU (``tests/golden/make_golden.py``, SURVEY.md §8(c) recipe).  ``attn_probe.py`` (dense
+float64 attention references and exact-answer probe inputs) restates nothing of the reference's:
+``tests/test_attn_probe_cpu.py`` checks it against autograd and the probes' closed forms.
 
 Pieces whose reference arithmetic lives in third-party libraries absent from the image
 (rotary-embedding-torch ``'pixel'`` freqs for OrthoRoPE, diffusers' FlowMatchEuler schedule)
