@@ -43,12 +43,6 @@
 #include "attn_fused_common.hpp"
 
 
-// timing-only experiment builds (tools/build_variant.sh -DOWLK_FUSED_EXP=n; results are WRONG):
-// bit 0: no hand-off (no flag polls, no sum loads); bit 1: no dQ products / stores either;
-// bit 2: no dS image writes
-#ifndef OWLK_FUSED_EXP
-#define OWLK_FUSED_EXP 0
-#endif
 // timing-only statistics build: workspace int32 words 10 / 11 count the hand-offs that found the
 // flag down at mid-step (blocking poll at the next step's top) / all hand-offs, per wave
 #ifndef OWLK_FUSED_STATS
@@ -462,7 +456,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
       f32x4 a[NACC];
 #pragma unroll
       for (int e = 0; e < NACC; ++e) a[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (j > jlo_at(i) && !(OWLK_FUSED_EXP & 1)) {
+      if (j > jlo_at(i)) {
         if (OWLK_FUSED_STATS && lane == 0) {
           __hip_atomic_fetch_add(p.hdr + 11, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (!ready) __hip_atomic_fetch_add(p.hdr + 10, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -495,10 +489,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
     for (int t = t_hi; t >= t_lo; --t) {
       const int q0 = t * FQT;
       const unsigned long long c0 = OWLK_FUSED_PROF ? __builtin_amdgcn_s_memtime() : 0ull;
-      const bool dq_on = !(OWLK_FUSED_EXP & 2) && t + 1 <= t_hi && dq_wave;
+      const bool dq_on = t + 1 <= t_hi && dq_wave;
       // the predecessor's sum of tile t + 1 (waits for this wave's vector memory: before any DMA)
       if (dq_on) dq_begin(t + 1);
-      const bool poll = j > jlo_at(t) && dq_wave && !(OWLK_FUSED_EXP & 1);
+      const bool poll = j > jlo_at(t) && dq_wave;
 
       int kind = TILE_FULL;
       if (t < full_lo || t >= full_hi) {
@@ -631,10 +625,8 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
           // 32 qb + 4 g .. + 3 (elements 0..3) and 32 qb + 16 + 4 g .. + 3 (elements 4..7) of key c
 #pragma unroll
           for (int t2 = 0; t2 < 2; ++t2) {
-            if (!(OWLK_FUSED_EXP & 4)) {
-              ds_put(t2, qb, 0, __builtin_shufflevector(sf[t2], sf[t2], 0, 1, 2, 3));
-              ds_put(t2, qb, 1, __builtin_shufflevector(sf[t2], sf[t2], 4, 5, 6, 7));
-            }
+            ds_put(t2, qb, 0, __builtin_shufflevector(sf[t2], sf[t2], 0, 1, 2, 3));
+            ds_put(t2, qb, 1, __builtin_shufflevector(sf[t2], sf[t2], 4, 5, 6, 7));
           }
           // dV / dK (the dS stores above are younger than every read waited for: the counts
           // only over-wait)
@@ -682,7 +674,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
 
     // ---- epilogue: dQ of tile t_lo (its dS image is in LDS)
     const unsigned long long cd = OWLK_FUSED_PROF ? __builtin_amdgcn_s_memtime() : 0ull;
-    const bool dq_epi = !(OWLK_FUSED_EXP & 2) && dq_wave;
+    const bool dq_epi = dq_wave;
     if (dq_epi) dq_begin(t_lo);
     // the next item's claim on this XCD's queue: its return is waited for with the dQ stores
     int npf = 0;

@@ -19,55 +19,29 @@ between them at a fixed place:
 
 Registers are fixed here, not by hipcc: the statement clobbers v[112:255] and the AGPR file; the
 accumulators dK^T / dV^T and the K' / V' fragments are compiler-allocated AGPR operands (they
-stay in a[0:191]).  The generator counts every LDS operation (in-order completion; lgkmcnt is
-4 bits, so counts above 15 over-wait) and pads the MFMA hazards with s_nop:
-  VALU write -> MFMA read: 2 wait states; 16x16x32 MFMA write -> VALU / LDS read: 8 (hipcc's own
-  padding on gfx950); MFMA read or write -> VALU / LDS-load write of that register: 12 (margin).
+stay in a[0:191]).  The LDS waits and the MFMA hazard padding are inserted by asmgen.finalize.
 """
 import argparse
-import re
 import os
 import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+from asmgen import Ins, vr, ar, rng, finalize  # noqa: E402
+
+REPO = os.path.dirname(HERE)
 OUT = os.path.join(REPO, "owl-audio-exps_amd", "csrc", "attn_bwd_fused4_step.inc")
-# schedule knobs for A/B builds (tools/build_f4_variants.sh): the 16x16x32 MFMA the hand-off check goes
-# before, the first MFMA of the ring DMA pieces and their spacing
-KNOB = {k: int(os.environ.get("F4_" + k.upper(), v))
-        for k, v in (("check", 96), ("dma0", 3), ("dmastep", 4), ("pro", 0), ("dqslots", 4), ("xnodma", 0),
-                     ("xnodqr", 0), ("ringv", 0), ("rvl", 49), ("flagall", 0), ("xprep", 0), ("xend", 0),
-                     ("xbar", 0), ("xexp", 0), ("pollpos", 0), ("xdmaconst", 0), ("chkpoll", 0))}  # x*: timing-only experiments (results wrong)
+# placement of the shipped schedule: the 16x16x32 MFMA the hand-off check goes before, the first MFMA
+# of the ring DMA pieces and their spacing, the slots of the dQ operand ring
+CHECK_AT = 96
+DMA_FIRST = 3
+DMA_STEP = 4
+DQ_SLOTS = 4
 
 TILE_BYTES = 64 * 128
 VLO = 96  # the statement's VGPRs: v[VLO:255]
 FQT = 64
 MF = "v_mfma_f32_16x16x32_bf16"
-
-
-class Ins:
-    __slots__ = ("text", "kind", "reads", "writes", "lds", "cost", "mfma_c", "passes")
-
-    def __init__(self, text, kind, reads=(), writes=(), lds=False, cost=4, mfma_c=(), passes=4):
-        self.text = text
-        self.kind = kind  # mfma | valu | exp | ldsr | ldsw | cmp | nop | wait | salu
-        self.reads = list(reads)  # physical registers ('v', n) / ('a', n)
-        self.writes = list(writes)
-        self.lds = lds
-        self.cost = cost
-        self.mfma_c = list(mfma_c)  # registers read as the accumulator input (chain)
-        self.passes = passes
-
-
-def vr(lo, n):
-    return [("v", lo + i) for i in range(n)]
-
-
-def ar(lo, n):
-    return [("a", lo + i) for i in range(n)]
-
-
-def rng(f, lo, n):
-    return f"{f}[{lo}:{lo + n - 1}]" if n > 1 else f"{f}{lo}"
 
 
 # ---------------------------------------------------------------- register plan
@@ -121,8 +95,8 @@ QA = 96  # the dQ^T accumulator (32 d x 32 q, v_mfma_f32_32x32x16_bf16): v[96:11
 MF32 = "v_mfma_f32_32x32x16_bf16"
 
 
-def DQR(s):  # dQ operand ring (4 or 5 slots x 8): K^T fragment +0..3, dS^T fragment +4..7; tq_0's
-    return (216, 224, 232, 240, 248)[s]  # registers (+ tq_1's last group), free until M1_1
+def DQR(s):  # dQ operand ring (DQ_SLOTS x 8): K^T fragment +0..3, dS^T fragment +4..7; tq_0's
+    return (216, 224, 232, 240)[s]  # registers, free until M1_1
 
 
 def stamp(i):
@@ -173,14 +147,14 @@ def build(kind, local, prof=False, P=0):
     # the previous tile's dQ^T[32 d x 32 q] += K^T[32 d x 16 keys] dS^T[16 keys x 32 q] over the item's
     # 256 keys (attn_bwd_fused_k's dq_mfma, same order): 16 MFMAs, one between every two of M1_0's
     dq = []
-    NS = KNOB["dqslots"]
+    NS = DQ_SLOTS
     for k2 in range(16):
         r = DQR(k2 % NS)
         dq.append(Ins(f"{MF32} {rng('v', QA, 16)}, {rng('a', r, 4)}, {rng('a', r + 4, 4)}, {rng('v', QA, 16)}", "mfma",
                       reads=ar(r, 8) + vr(QA, 16), writes=vr(QA, 16), mfma_c=vr(QA, 16), passes=8))
     stream = []  # (Ins, small index or None)
     for i in range(128):
-        if i < 32 and i % 2 == KNOB["pro"]:
+        if i < 32 and i % 2 == 0:
             stream.append((dq[i // 2], None))
         stream.append((mf[i], i))
     pos = {i: n for n, (_, i) in enumerate(stream) if i is not None}
@@ -232,8 +206,8 @@ def build(kind, local, prof=False, P=0):
         out = []
         st0, dp0 = ST(h, t4, 0), DP(h, t4, 0)
         for i in range(8):  # P = exp2(-(lse2 - c s))
-            out.append(Ins(f"v_exp_f32_e64 v{st0 + i}, -v{st0 + i}" if not KNOB["xexp"] else f"v_mov_b32 v{st0 + i}, v{st0 + i}",
-                           "exp", reads=vr(st0 + i, 1), writes=vr(st0 + i, 1), cost=8))
+            out.append(Ins(f"v_exp_f32_e64 v{st0 + i}, -v{st0 + i}", "exp", reads=vr(st0 + i, 1), writes=vr(st0 + i, 1),
+                           cost=8))
         if masked:
             # query row 32 h + 16 qs + 4 g + r of the tile is allowed for key tile t4 iff lo <= . < hi,
             # with %[mlo{t4}] / %[mhi{t4}] = bound - 4 g (per lane)
@@ -281,22 +255,9 @@ def build(kind, local, prof=False, P=0):
     # statement) against want (INT_MAX when the tile has no predecessor to wait for); on a match the predecessor's sum goes to the landing zone (4 LDS-DMA
     # pieces, sc1), to be consumed by the next step.  The dQ stores are the 4 youngest vector-memory
     # operations here, so vmcnt(4) waits for the poll (and the ring's DMA, issued before it)
-    def check(ringw=False):
+    def check():
         tmp = LR(0, 0)
-        # (a poll placed after the dQ stores: nothing younger than it at the check)
-        out = [Ins("s_waitcnt vmcnt(0)" if KNOB["pollpos"] > 32 and kind != "empty" else "s_waitcnt vmcnt(4)", "raw")]
-        if KNOB["chkpoll"] and kind != "empty" and not KNOB["pollpos"]:
-            # wait for the poll alone: the ring's DMA (4 or 5 pieces, flags bit 1) and the dQ stores
-            # after it may still fly (the end of the step waits for them)
-            out = [Ins("s_bitcmp1_b32 %[fl], 1\ns_cbranch_scc0 .Lf4c4%=\ns_waitcnt vmcnt(8)\ns_branch .Lf4c5%=\n"
-                       ".Lf4c4%=:\ns_waitcnt vmcnt(4)\n.Lf4c5%=:", "raw")]
-        if ringw:  # the next tile's ring rows, staged in v[112:127] / v96 since rvl, into the other slot
-            t = ["s_waitcnt vmcnt(0)", "s_bitcmp1_b32 %[fl], 1", "s_cbranch_scc0 .Lf4rw%="]
-            t += [f"ds_write_b128 %[rq], {rng('v', 112 + 4 * i, 4)} offset:{SN + (TILE_BYTES if i >= 2 else 0) + 1024 * (i % 2)}"
-                  for i in range(4)]
-            t += ["s_bitcmp1_b32 %[fl], 2", "s_cbranch_scc0 .Lf4rw%=", f"ds_write_b32 %[rl], v96 offset:{SN}", ".Lf4rw%=:"]
-            out = [Ins("\n".join(t), "raw", reads=vr(112, 16) + vr(96, 1))]  # (LDS ops not counted: later waits over-wait)
-        out += [
+        out = [Ins("s_waitcnt vmcnt(4)", "raw"),
                Ins(f"ds_read_b32 v{tmp}, %[flagv]", "ldsr", writes=vr(tmp, 1), lds=True),
                Ins(f"v_readfirstlane_b32 %[tmp], v{tmp}", "valu", reads=vr(tmp, 1))]
         t = ["s_nop 3", "s_mov_b32 %[lout], 0",
@@ -314,8 +275,6 @@ def build(kind, local, prof=False, P=0):
     # the ring's LDS-DMA of the next tile (t - 1, into the other slot): 2 Q + 2 dO rows-pieces per wave
     # (rows 16 w + 8 h ..), the lse2 (wave 0) / delta (wave 1) row; flags bit 1 / bit 2
     def dma_piece(i):
-        if KNOB["xnodma"]:
-            return Ins("s_nop 0", "raw")
         if i < 4:
             src, off = ("qb", f"qo{i % 2}") if i < 2 else ("ob", f"oo{i % 2}")
             dst = SN + (TILE_BYTES if i >= 2 else 0) + 1024 * (i % 2)
@@ -349,14 +308,9 @@ def build(kind, local, prof=False, P=0):
     N = len(stream)
     fill = [[] for _ in range(N + 1)]
     # prologue: the dQ sum, dQ k-step 0, rows and ring group 0 of half 0, k-step 1, ring group 1, k-step 2
-    # (pro 1: the first S / dP operands first, and the stream opens with two 16x16x32 MFMAs)
     ahead = NS - 1
-    if KNOB["pro"]:
-        pro += rd_rows(0)[0:2] + rd_group(0) + rd_qacc() + rd_dq(0) + rd_rows(0)[2:4] + rd_group(1)
-        pro += sum((rd_dq(k) for k in range(1, ahead)), [])
-    else:
-        pro += rd_qacc() + rd_dq(0) + rd_rows(0)[0:2] + rd_group(0) + rd_rows(0)[2:4] + rd_dq(1) + rd_group(1)
-        pro += sum((rd_dq(k) for k in range(2, ahead)), [])
+    pro += rd_qacc() + rd_dq(0) + rd_rows(0)[0:2] + rd_group(0) + rd_rows(0)[2:4] + rd_dq(1) + rd_group(1)
+    pro += sum((rd_dq(k) for k in range(2, ahead)), [])
     # dQ k-step k2 + NS - 1 right after dQ MFMA k2 (NS-slot ring)
     for k2 in range(16 - ahead):
         fill[dpos[k2] + 1] += rd_dq(k2 + ahead)
@@ -373,20 +327,12 @@ def build(kind, local, prof=False, P=0):
     for ds in range(4):
         fill[pos[36 + 6 * ds]] += rd_tr(0, ds)
         fill[pos[66 + 6 * ds]] += rd_tr(1, ds)
-    if KNOB["ringv"]:  # the ring rows by plain loads into v[112:127] (free after half 1's first chains) / v96
-        t = ["s_bitcmp1_b32 %[fl], 1", "s_cbranch_scc0 .Lf4rv%="]
-        t += [f"global_load_dwordx4 {rng('v', 112 + 4 * i, 4)}, %[{('qo', 'oo')[i // 2]}{i % 2}], %[{('qb', 'ob')[i // 2]}]"
-              for i in range(4)]
-        t += ["s_bitcmp1_b32 %[fl], 2", "s_cbranch_scc0 .Lf4rv%=", "global_load_dword v96, %[lo], %[lb]", ".Lf4rv%=:"]
-        fill[pos[KNOB["rvl"]]].append(Ins("\n".join(t), "raw", writes=vr(112, 16) + vr(96, 1)))
-        fill[pos[KNOB["check"]]] = check(True) + fill[pos[KNOB["check"]]]
-    else:
-        fill[pos[KNOB["check"]]] = check() + fill[pos[KNOB["check"]]]
-        for i in range(5):  # the ring's DMA between the MFMAs of M1_0 + dQ (no VALU there)
-            fill[pos[KNOB["dma0"] + KNOB["dmastep"] * i]].append(dma_piece(i))
+    fill[pos[CHECK_AT]] = check() + fill[pos[CHECK_AT]]
+    for i in range(5):  # the ring's DMA between the MFMAs of M1_0 + dQ (no VALU there)
+        fill[pos[DMA_FIRST + DMA_STEP * i]].append(dma_piece(i))
     if prof:  # s_memtime at the block boundaries (SMEM: one outstanding keeps every lgkmcnt wait safe)
         fill[pos[32]].append(stamp(1))
-        fill[pos[64]].insert(0, stamp(2))  # (after a check placed at 64)
+        fill[pos[64]].insert(0, stamp(2))
         fill[pos[96]].insert(0, stamp(3))
     # VALU: half 0 chunks paced over MFMAs 33 .., half 1 after; chunk (h, t4) due before MFMA 64 + 32 h + 8 t4
     vstream = []
@@ -405,10 +351,7 @@ def build(kind, local, prof=False, P=0):
             gap = min(gap, due)
             fill[pos[gap]].append(x)
             k += 1
-    if KNOB["pollpos"]:
-        fill[pos[KNOB["pollpos"]]] += poll
-    prog = [Ins("s_waitcnt lgkmcnt(0)", "wait"), Ins("s_nop 3", "nop")] + ([stamp(0)] if prof else []) + \
-        ([] if KNOB["pollpos"] else poll) + pro
+    prog = [Ins("s_waitcnt lgkmcnt(0)", "wait"), Ins("s_nop 3", "nop")] + ([stamp(0)] if prof else []) + poll + pro
     for n in range(N):
         prog += fill[n]
         prog.append(stream[n][0])
@@ -418,109 +361,9 @@ def build(kind, local, prof=False, P=0):
     return prog
 
 
-def finalize(prog, allow_pending=False):
-    """Insert lgkmcnt waits and hazard nops; returns the instruction texts and statistics.  allow_pending:
-    LDS loads may still fly at the end (the caller drains them with lgkmcnt(0) before their use)."""
-    out = []
-    # LDS bookkeeping
-    issued = 0          # LDS ops issued so far
-    done_upto = 0       # all LDS ops with index < done_upto are known complete
-    pending = {}        # register -> LDS op index that writes it (loads not yet waited for)
-    # hazard bookkeeping: per register (position in wait states) of last write / MFMA access
-    pos = 0
-    last_w = {}   # reg -> (pos, kind)
-    last_mfma = {}  # reg -> pos of the last MFMA reading it as the accumulator or writing it
-    last_ab = {}    # reg -> pos of the last MFMA reading it as the A / B operand
-    nops = waits = 0
-
-    def ws_since(p):
-        return pos - p - 1  # instructions strictly between
-
-    for ins in prog:
-        if ins.kind == "wait":
-            out.append(ins.text)
-            pos += 1
-            if "lgkmcnt(0)" in ins.text:
-                done_upto = issued
-                pending.clear()
-            continue
-        # 1. LDS results this instruction consumes
-        need = -1
-        for r in ins.reads:
-            if r in pending:
-                need = max(need, pending[r])
-        if ins.lds and ins.kind == "ldsr":
-            # WAR on its destination against an older LDS read of the same registers is ordered (in-order)
-            pass
-        if need >= done_upto:
-            cnt = issued - need - 1
-            cnt = min(cnt, 15)
-            out.append(f"s_waitcnt lgkmcnt({cnt})")
-            waits += 1
-            pos += 1
-            done_upto = issued - cnt
-            for r in list(pending):
-                if pending[r] < done_upto:
-                    del pending[r]
-        # 2. hazards
-        pad = 0
-        if ins.kind == "mfma":
-            for r in ins.reads:
-                if r in ins.mfma_c and last_w.get(r, (-99, "", 0))[1] == "mfma":
-                    continue  # accumulate chain
-                w = last_w.get(r)
-                if w and w[1] in ("valu", "exp"):
-                    pad = max(pad, 2 - ws_since(w[0]))
-                if w and w[1] == "mfma":
-                    pad = max(pad, w[2] + 4 - ws_since(w[0]))
-            for r in ins.writes:
-                w = last_w.get(r)
-                if w and w[1] in ("valu", "exp"):
-                    pad = max(pad, 2 - ws_since(w[0]))
-        else:
-            for r in ins.reads:
-                w = last_w.get(r)
-                if w and w[1] == "mfma":
-                    pad = max(pad, w[2] - ws_since(w[0]))
-            for r in ins.writes:
-                m = last_mfma.get(r)
-                if m is not None:
-                    pad = max(pad, 12 - ws_since(m))
-                m = last_ab.get(r)
-                if m is not None:
-                    pad = max(pad, 2 - ws_since(m))
-        while pad > 0:
-            n = min(pad, 8)
-            out.append(f"s_nop {n - 1}")
-            pos += n
-            pad -= n
-            nops += 1
-        # 3. issue (a raw block -- branches, stores -- counts as one wait state: its shortest path)
-        out += ins.text.split("\n")
-        if ins.lds:
-            idx = issued
-            issued += 1
-            if ins.kind == "ldsr":
-                for r in ins.writes:
-                    pending[r] = idx
-        for r in ins.writes:
-            last_w[r] = (pos, "mfma" if ins.kind == "mfma" else ("ld" if ins.kind == "ldsr" else "valu"),
-                         12 if ins.passes == 8 else 8)
-        if ins.kind == "mfma":
-            for r in ins.mfma_c + ins.writes:
-                last_mfma[r] = pos
-            for r in ins.reads:
-                if r not in ins.mfma_c:
-                    last_ab[r] = pos
-        m = re.match(r"s_nop (\d+)", ins.text)
-        pos += int(m.group(1)) + 1 if m else 1
-    # end: the last MFMAs' results / operands are the compiler's again after the statement
-    out.append("s_nop 7")
-    out.append("s_nop 3")
-    assert allow_pending or not pending, "LDS loads never waited for"
-    return out, dict(nops=nops, waits=waits, instrs=len(out))
-
-
+# (rq / rl: no statement reads them any more -- they belonged to a rejected schedule -- but they are
+# live inputs of every statement, so hipcc keeps two VGPRs for them; taking them out changes the
+# kernel's register allocation and needs its own measurement)
 VOPS = ["ar0", "ar1", "al", "tr0", "tr1", "tr2", "tr3", "ds0", "ds1", "ds2", "ds3", "qa", "kf", "sa", "sb", "soffa",
         "soffr", "flagv", "qo0", "qo1", "oo0", "oo1", "lo", "zero", "rq", "rl"]
 SOPS = [("rsrc", "__amdgpu_buffer_rsrc_t"), ("fl", "int"), ("nscale", "float"), ("want", "int"), ("soffs", "int"),
@@ -587,28 +430,21 @@ def emit_run(local):
     t = ["s_waitcnt vmcnt(0)", "s_cmp_eq_u32 %[par], 0", "s_cbranch_scc0 .Lf4L1%="]
     for P in (0, 1):
         t += [f".Lf4L{P}%=:", "s_bitcmp1_b32 %[fl], 3", f"s_cbranch_scc0 .Lf4z{P}%=",
-              "s_cmp_eq_u32 %[lout], 0", "s_cbranch_scc1 .Lf4x%=",
-              "s_nop 0" if KNOB["xprep"] else ("s_waitcnt vmcnt(1)" if KNOB["flagall"] else "s_waitcnt vmcnt(0)"),
+              "s_cmp_eq_u32 %[lout], 0", "s_cbranch_scc1 .Lf4x%=", "s_waitcnt vmcnt(0)",
               f"s_branch .Lf4pd{P}%=", f".Lf4z{P}%=:"]
         t += [f"v_mov_b32 v{112 + i}, 0" for i in range(4)]
         t += [f"ds_write_b128 %[qa], v[112:115] offset:{1024 * e}" for e in range(4)]
         t += [f".Lf4pd{P}%=:"] + bodies[P]
-        if KNOB["xend"]:
-            t += ["s_waitcnt lgkmcnt(0)", "s_barrier"]
-        else:
-            t += ["s_cmp_eq_u32 %[lout], 0", f"s_cbranch_scc1 .Lf4v{P}%=", "s_waitcnt vmcnt(4)", f"s_branch .Lf4w{P}%=",
-                  f".Lf4v{P}%=:", "s_waitcnt vmcnt(0)", f".Lf4w{P}%=:", "s_waitcnt lgkmcnt(0)", "s_barrier"]
-        if KNOB["xbar"]:
-            t[-1] = "s_nop 0"
-        t += [
+        t += ["s_cmp_eq_u32 %[lout], 0", f"s_cbranch_scc1 .Lf4v{P}%=", "s_waitcnt vmcnt(4)", f"s_branch .Lf4w{P}%=",
+              f".Lf4v{P}%=:", "s_waitcnt vmcnt(0)", f".Lf4w{P}%=:", "s_waitcnt lgkmcnt(0)", "s_barrier",
               # lane 0 of wave 0 raises the flag of tile t + 1 (every wave's dQ stores are done)
-              ] + (["s_cmp_eq_u32 %[wid], 0", f"s_cbranch_scc0 .Lf4f{P}%="] if not KNOB["flagall"] else []) + [
+              "s_cmp_eq_u32 %[wid], 0", f"s_cbranch_scc0 .Lf4f{P}%=",
               "s_mov_b64 s[78:79], exec", "s_mov_b64 exec, 1",
               "global_store_dword %[zero], %[fval], %[fb] offset:64 sc1", "s_mov_b64 exec, s[78:79]", f".Lf4f{P}%=:",
-              ] + ([] if KNOB["xdmaconst"] else [
+              # every pointer back one tile
               "s_sub_u32 s64, s64, %[qstep]", "s_subb_u32 s65, s65, 0",
               "s_sub_u32 s66, s66, %[ostep]", "s_subb_u32 s67, s67, 0",
-              "s_sub_u32 s68, s68, 256", "s_subb_u32 s69, s69, 0"]) + [
+              "s_sub_u32 s68, s68, 256", "s_subb_u32 s69, s69, 0",
               "s_sub_u32 s70, s70, 64", "s_subb_u32 s71, s71, 0",
               "s_sub_u32 s72, s72, 0x4000", "s_subb_u32 s73, s73, 0",
               "s_sub_u32 s74, s74, 0x4000",
