@@ -109,11 +109,14 @@ int owlk_adaln_fwd(const void* x, long ldx, const void* scale, const void* shift
                    long T, int d, void* y, long ldy, float* rstd, void* yact /* optional bf16(silu(y)),
                    FinalLayer attn.py:272-277 */, void* stream);
 /* backward: dx = rms_norm' (dy * (1 + scale)) (+ dres); dscale[f] = sum_t dy*xn; dshift[f] = sum_t dy
- *   (fp32, or bf16 with mod_bf16 = 1: straight into a bf16 modulation-gradient matrix, row stride ldg) */
+ *   (fp32, or bf16 with mod_bf16 = 1: straight into a bf16 modulation-gradient matrix, row stride ldg).
+ *   ypre (FinalLayer: dy arrives as d silu(ypre)) has no row stride of its own: it is a [T, d] bf16 view
+ *   read with dy's row stride lddy, so it must be laid out like dy. */
 int owlk_adaln_bwd(const void* dy, long lddy, const void* x, long ldx, const float* rstd,
                    const void* scale, long ldm, long tpf, long T, int d, const void* dres, long ldres,
                    void* dx, long lddx, void* dscale, void* dshift, long ldg,
-                   const void* ypre /* optional: dy is d silu(ypre) */, int mod_bf16, void* stream);
+                   const void* ypre /* optional: dy is d silu(ypre); row stride lddy */, int mod_bf16,
+                   void* stream);
 
 /* ---- Gate backward (modulation.py:28-43 Gate / :57-63 cond_gate; forward is GEMM epi 2):
  *   dy = bf16(dout * g[t/tpf]); dg[f] = sum_t dout*y (row stride lddg; fp32, or bf16 with dg_bf16 = 1);

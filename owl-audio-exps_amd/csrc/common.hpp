@@ -129,9 +129,13 @@ int colsum_reduce(const float* part, int splits, long N, float* out, hipStream_t
     }                                       \
   } while (0)
 
-static constexpr int MAXCPL = 8;  // max 16-B chunks per lane (d <= 4096)
+// max 16-B chunks per lane: rows up to d = 64 * 8 * MAXCPL = 4096 (there the row-loop backward kernels ask
+// for 8 d floats = 128 KiB of dynamic LDS, which gfx950 grants).  The dispatch below does not check d: every
+// entry that uses it refuses a wider row first, with a message (OWLK_REQUIRE(d <= 64 * 8 * MAXCPL, ...)).
+static constexpr int MAXCPL = 8;
 
-// launch helper: pick the chunks-per-lane instantiation for a row width d
+// launch helper: pick the chunks-per-lane instantiation for a row width d (7 chunks take <8>, whose
+// `c < nch` guards leave the top chunk idle)
 #define OWLK_CPL_DISPATCH(d, KERNEL, ...)                     \
   do {                                                        \
     const int cpl_ = ((d) / 8 + 63) / 64;                     \

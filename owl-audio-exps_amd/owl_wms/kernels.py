@@ -198,10 +198,23 @@ def adaln_fwd(x, scale, shift, tpf, act=False):
     return (y, rstd, ya) if act else (y, rstd)
 
 
+def _adaln_bwd_rows(dy, x, ypre):
+    """owlk_adaln_bwd's row contract: dy / x unit column stride, and ypre read with dy's row stride
+    (the C ABI has no ldypre), so it must be a [T, d] view laid out like dy."""
+    assert dy.shape == x.shape and dy.stride(1) == 1 and x.stride(1) == 1, \
+        f"adaln_bwd: dy / x must be [T, d] row views (got {dy.shape}/{dy.stride()}, {x.shape}/{x.stride()})"
+    if ypre is not None:
+        assert ypre.dtype == BF16 and ypre.shape == dy.shape and ypre.stride() == dy.stride(), \
+            f"adaln_bwd: ypre shares dy's shape and row stride (got {ypre.shape}/{ypre.stride()} vs " \
+            f"{dy.shape}/{dy.stride()})"
+
+
 def adaln_bwd(dy, x, rstd, scale, tpf, dres=None, ypre=None):
-    """-> dx [T, d] bf16 (+ dres), dmod [F, 2d] fp32 (= [dscale | dshift])."""
+    """-> dx [T, d] bf16 (+ dres), dmod [F, 2d] fp32 (= [dscale | dshift]).  ypre (FinalLayer: dy is
+    d silu(ypre)) is read with dy's row stride."""
     T, d = x.shape
     F_ = T // tpf
+    _adaln_bwd_rows(dy, x, ypre)
     dx = torch.empty(T, d, device=x.device, dtype=BF16)
     dmod = torch.empty(F_, 2 * d, device=x.device, dtype=F32)
     call("owlk_adaln_bwd", ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(rstd), ptr(scale), scale.stride(0), tpf,
@@ -212,8 +225,9 @@ def adaln_bwd(dy, x, rstd, scale, tpf, dres=None, ypre=None):
 
 def adaln_bwd_into(dy, x, rstd, scale, tpf, dmod, dres=None, ypre=None):
     """adaln_bwd writing [dscale | dshift] as bf16 straight into dmod (a [F, 2d] bf16 view of a
-    modulation-gradient matrix, any row stride) -> dx [T, d] bf16."""
+    modulation-gradient matrix, any row stride) -> dx [T, d] bf16.  ypre is read with dy's row stride."""
     T, d = x.shape
+    _adaln_bwd_rows(dy, x, ypre)
     assert dmod.dtype == BF16 and dmod.shape == (T // tpf, 2 * d) and dmod.stride(1) == 1
     dx = torch.empty(T, d, device=x.device, dtype=BF16)
     call("owlk_adaln_bwd", ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(rstd), ptr(scale), scale.stride(0), tpf,

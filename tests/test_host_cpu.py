@@ -623,3 +623,27 @@ def test_bench_dump_outputs_arrays(tmp_path):
     assert np.array_equal(a["params"][DUMP_PER_TENSOR:], tail)
     w = model[0].weight.detach().reshape(-1).float().numpy()
     assert np.isin(a["params"][:DUMP_PER_TENSOR], w).all()
+
+
+def test_adaln_bwd_wrappers_check_the_ypre_row_contract():
+    """owlk_adaln_bwd reads ypre with dy's row stride (include/owlk.h): the wrappers refuse, before any
+    launch, a ypre that is not laid out like dy, and dy / x without unit column stride."""
+    from owl_wms import kernels as k
+    T, d = 6, 16
+    bf = torch.bfloat16
+    dy, x = torch.zeros(T, d, dtype=bf), torch.zeros(T, d, dtype=bf)
+    wide = torch.zeros(T, d + 8, dtype=bf)
+    rstd, scale = torch.ones(T), torch.zeros(2, d, dtype=bf)
+    dmod = torch.zeros(2, 2 * d, dtype=bf)
+    for ypre in (wide[:, :d], torch.zeros(T - 1, d, dtype=bf), torch.zeros(T, d)):
+        with pytest.raises(AssertionError, match="ypre"):
+            k.adaln_bwd(dy, x, rstd, scale, 3, ypre=ypre)
+        with pytest.raises(AssertionError, match="ypre"):
+            k.adaln_bwd_into(dy, x, rstd, scale, 3, dmod, ypre=ypre)
+    with pytest.raises(AssertionError, match="ypre"):
+        k.adaln_bwd(wide[:, :d], x, rstd, scale, 3, ypre=torch.zeros(T, d, dtype=bf))
+    for bad_dy, bad_x in ((torch.zeros(d, T, dtype=bf).t(), x), (dy, torch.zeros(d, T, dtype=bf).t())):
+        with pytest.raises(AssertionError, match="row views"):
+            k.adaln_bwd(bad_dy, bad_x, rstd, scale, 3)
+        with pytest.raises(AssertionError, match="row views"):
+            k.adaln_bwd_into(bad_dy, bad_x, rstd, scale, 3, dmod)

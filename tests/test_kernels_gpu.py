@@ -1069,7 +1069,11 @@ def test_mlp_custom_unaligned_wide_input(k_in):
 
 
 @pytest.mark.parametrize("d,tpf,F,bias", [(1536, 64, 6, True), (128, 1, 40, False), (2560, 65, 2, True),
-                                          (1536, 2, 9, True)])
+                                          (1536, 2, 9, True),
+                                          # every chunks-per-lane case of the fused kernel's own dispatch switch
+                                          (8, 65, 2, True), (136, 3, 3, True), (520, 4, 3, False), (1000, 5, 3, True),
+                                          (1024, 1, 3, True), (2048, 65, 2, True), (3080, 5, 3, True),
+                                          (4096, 3, 2, False), (4096, 65, 2, True)])
 def test_adaln_gate_bwd_fused_equals_two_passes(d, tpf, F, bias):
     """owlk_adaln_gate_bwd: the AdaLN backward and the gate backward on its dx in one pass, bit for bit
     the two separate kernels (dx, dscale | dshift, the gated dy, dg, the bias partials)."""
