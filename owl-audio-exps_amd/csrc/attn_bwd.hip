@@ -8,9 +8,11 @@
 // Two deterministic kernels (no float atomics):
 //   dkdv : workgroup = 4 waves x 32 keys; sweeps 64-query tiles; S, dP with the key on the lane
 //          (Q/dO rows x K/V in registers), then dV^T += dO^T P and dK^T += Q^T dS take P / dS
-//          straight from the accumulators as B operands.
-//   dq   : workgroup = 4 waves x 32 queries; sweeps 64-key tiles like the forward (query on the
-//          lane), dQ^T += K^T dS^T with K^T fragments through ds_read_b64_tr_b16.
+//          straight from the accumulators as B operands.  attn_bwd_dkdv16_k (D 64, 16x16x32 MFMAs)
+//          and attn_bwd_dkdv_k (D 128, 32x32x16 MFMAs, one wave per SIMD).
+//   dq   : workgroup = 4 waves x 32 or 48 queries; sweeps 64-key tiles like the forward (query on
+//          the lane), dQ^T += K^T dS^T with K^T fragments through ds_read_b64_tr_b16
+//          (attn_bwd_dq16_k, 16x16x32 MFMAs, both head dims).
 #include "attn_common.hpp"
 
 
@@ -60,11 +62,11 @@ DEV void store_rowT(bf16* dst, const f32x16 (&acc)[NDB], float mul, int h) {
 }
 
 // ======================================================================== dK, dV
-// Query tiles of QT x 64 rows per ring slot.  QT = 2 (D 64, unwindowed masks: two-slot ring,
-// 66 KiB per workgroup, two workgroups per CU) pays the per-tile fixed costs (DMA issue, ring
-// bookkeeping, the workgroup barrier) once per 64 MFMAs: global layers -2.5 %.  Windowed (local)
-// layers keep QT = 1 and the three-slot ring: their short sweeps are dominated by mask-edge
-// tiles, which QT = 2 makes twice as large (+60 % measured there).
+// Query tiles of QT x 64 rows per ring slot.  QT = 2 (long sweeps: two-slot ring; at D 64 66 KiB
+// per workgroup, two workgroups per CU; at D 128 130 KiB, one) pays the per-tile fixed costs (DMA
+// issue, ring bookkeeping, the workgroup barrier) once per two 64-row tiles: global layers -2.5 %
+// at D 64.  Short windowed (local) sweeps keep QT = 1 and the Cfg<D> ring: they are dominated by
+// mask-edge tiles, which QT = 2 makes twice as large (+60 % measured there).
 template <int D, int QT_>
 struct DkdvCfg {
   static constexpr int QT = QT_;
@@ -74,9 +76,8 @@ struct DkdvCfg {
 
 // FULL tiles (no mask bits): the 2 QT blocks of 32 query rows x this wave's 32 keys run as a
 // software pipeline in one branch-free region, so the S / dP MFMAs of block i+1 issue while the
-// VALU turns block i's scores into P and dS (exp2, multiply, bf16 packing).  For the one-wave-
-// per-SIMD D 128 kernel, whose MFMA pipe has no partner wave to cover the softmax; at D 64 the
-// two co-resident waves already do that (+1 % measured there, so not used).
+// VALU turns block i's scores into P and dS (exp2, multiply, bf16 packing): the one-wave-per-SIMD
+// D 128 kernel's MFMA pipe has no partner wave to cover the softmax.
 template <class C, int QT>
 DEV void dkdv_full_pipelined(const char* tb, const float* l2, const float* dlt, const bf16x8 (&kf)[C::NS],
                              const bf16x8 (&vf)[C::NS], f32x16 (&dk)[C::NDB], f32x16 (&dv)[C::NDB], int lane) {
@@ -148,8 +149,10 @@ DEV void dkdv_full_pipelined(const char* tb, const float* l2, const float* dlt, 
   }
 }
 
-template <int D, int QT_, bool PIPE = false>
-__global__ __launch_bounds__(256, D == 64 ? 2 : 1) void attn_bwd_dkdv_k(BwdP p) {
+// D 128 only (dit_v4_5B): one wave per SIMD, accumulators in AGPRs; D 64 runs attn_bwd_dkdv16_k.
+template <int D, int QT_>
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkdv_k(BwdP p) {
+  static_assert(D == 128, "attn_bwd_dkdv_k is built for head_dim 128 only (D 64: attn_bwd_dkdv16_k)");
   using C = Cfg<D>;
   using G = DkdvCfg<D, QT_>;
   constexpr int QT = G::QT, TLQ = G::TLQ, NBUF = G::NBUF;
@@ -296,12 +299,13 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void attn_bwd_dkdv_k(BwdP p) 
     }
     kind = __builtin_amdgcn_readfirstlane(kind);
 
-    if constexpr (PIPE) {
-      if (kind == TILE_FULL) {
-        dkdv_full_pipelined<C, QT>(tb, l2, dlt, kf, vf, dk, dv, lane);
-        kind = TILE_EMPTY;  // done
-      }
+    if (kind == TILE_FULL) {
+      dkdv_full_pipelined<C, QT>(tb, l2, dlt, kf, vf, dk, dv, lane);
+      kind = TILE_EMPTY;  // done
     }
+    // mask-edge tiles.  `masked` is always true here; it stays a run-time value because hipcc, told
+    // that it is constant, allocates this kernel differently (256 + 256 registers and 380-648 B of
+    // scratch instead of 253 + 192 and none)
     if (kind != TILE_EMPTY) {
       const bool masked = kind == TILE_PARTIAL;
 #pragma unroll
@@ -366,7 +370,7 @@ __global__ __launch_bounds__(256, D == 64 ? 2 : 1) void attn_bwd_dkdv_k(BwdP p) 
 }
 
 // ======================================================================== dK, dV on 16x16x32 MFMAs
-// The same workgroup, ring and tile classes as attn_bwd_dkdv_k (D 64), with every product on
+// D 64: the same workgroup, ring and tile classes as attn_bwd_dkdv_k, with every product on
 // v_mfma_f32_16x16x32_bf16: the chip holds a higher clock on that shape than on 32x32x16 at the same
 // cycles per FLOP (MI355X_MICROARCH.md, DVFS give-back item 7).  Per wave 32 keys as two 16-key
 // column tiles (lane column c = lane & 15, k-group g = lane >> 4); per 32-query block two 16-row
@@ -612,194 +616,16 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv16_k(BwdP p) {
   }
 }
 
-// ======================================================================== dQ
-// Key tiles of QT x 64 rows per ring slot: QT = 2 (D 64, unwindowed masks; two-slot ring) pays the
-// per-tile fixed costs once per 48 MFMAs, as in the dK/dV kernel.
-#ifndef OWLK_DQ_INIT
-#define OWLK_DQ_INIT 1
-#endif
-template <int D, int QT>
-__global__ __launch_bounds__(256, D == 64 ? (OWLK_DQ_INIT ? 2 : 3) : 2) void attn_bwd_dq_k(BwdP p) {
-  constexpr bool INIT = OWLK_DQ_INIT && D == 64;
-  using C = Cfg<D>;
-  constexpr int NBUF = QT == 2 ? 2 : C::NBUF, TLK = TL * QT;
-  constexpr int BUF = 2 * QT * C::NSUB * SUB;  // K [QT] | V [QT]
-  __shared__ __attribute__((aligned(16))) char smem[NBUF * BUF + 16];  // + reduction slot (one object)
-  int& red_lo = *(int*)(smem + NBUF * BUF);
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int h = lane >> 5, ql = lane & 31;
-  const BlockIds bid = xcd_block_ids();
-  const long b = bid.z;
-  const int head = bid.y;
-  const int ntq = (int)((p.Lq + TB - 1) / TB);
-  const long q0 = (long)(ntq - 1 - bid.x) * TB;
-  const long r0 = q0 + 32 * w;
-  const MaskP& m = p.m;
-
-  const bf16* Q = p.q + b * p.sqb + head * D;
-  const bf16* K = p.k + b * p.skb + head * D;
-  const bf16* V = p.v + b * p.svb + head * D;
-  const bf16* dO = p.dout + b * p.sob + head * D;
-
-  const long qlast = (q0 + TB < p.Lq ? q0 + TB : p.Lq) - 1;
-  const int fq_lo = frame_of(m, q0 + m.q_offset), fq_hi = frame_of(m, qlast + m.q_offset);
-  int lo_f;
-  if (m.kv_lo) {
-    if (threadIdx.x == 0) red_lo = 1 << 30;
-    __syncthreads();
-    int mn = 1 << 30;
-    for (int f = fq_lo + threadIdx.x; f <= fq_hi; f += 256) mn = min(mn, m.kv_lo[b * m.fstride + f]);
-    atomicMin(&red_lo, mn);
-    __syncthreads();
-    lo_f = red_lo;
-  } else {
-    lo_f = m.window > 0 ? max(0, fq_lo - m.window + 1) : 0;
-  }
-  const int hi_f = m.causal ? fq_hi : (m.window > 0 ? min(m.n_frames - 1, fq_hi + m.window - 1) : m.n_frames - 1);
-  long kv_begin = ((long)lo_f * m.tpf / TL) * TL;
-  long kv_end = ((long)hi_f + 1) * m.tpf;
-  if (kv_end > p.Lkv) kv_end = p.Lkv;
-  const int ntiles = kv_end > kv_begin ? (int)((kv_end - kv_begin + TLK - 1) / TLK) : 0;
-
-  const long my_q = r0 + ql;
-  const bool qok = my_q < p.Lq;
-  bf16x8 qf[C::NS], df[C::NS];
-#pragma unroll
-  for (int s = 0; s < C::NS; ++s) {
-    qf[s] = qok ? *(const bf16x8*)(Q + my_q * p.ldq + 16 * s + 8 * h) : bf16x8{};
-    df[s] = qok ? *(const bf16x8*)(dO + my_q * p.ldo + 16 * s + 8 * h) : bf16x8{};
-  }
-  const float L2 = qok ? p.lse[(b * p.H + head) * p.Lq + my_q] : 0.f;  // base-2 lse (attn_fwd)
-  const float Dl = qok ? p.delta[(b * p.H + head) * p.Lq + my_q] : 0.f;
-  // OWLK_DQ_INIT: q' = bf16(c q) and constant accumulator-init registers -lse2 / -delta (the
-  // first MFMA of each chain reads them as C), so S' arrives as the exp2 argument and dP - delta
-  // needs no subtraction: 2 VALU per score instead of 4, for 32 more VGPRs (2 waves / SIMD)
-  f32x16 sinit, pinit;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    sinit[r] = -L2;
-    pinit[r] = -Dl;
-  }
-  if (INIT) {
-#pragma unroll
-    for (int s = 0; s < C::NS; ++s) {
-      float f[8];
-      unpack8(qf[s], f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] *= p.scale_log2;
-      qf[s] = pack8(f);
-    }
-  }
-  const bool wave_live = r0 < p.Lq;
-  const long wlast = (r0 + 31 < p.Lq ? r0 + 31 : p.Lq - 1);
-  const int wfq0 = frame_of(m, r0 + m.q_offset), wfq1 = frame_of(m, wlast + m.q_offset);
-  TileRange full = full_range_kv(m, b, wfq0, wfq1, kv_begin, p.Lkv, TLK);
-  if (!wave_live) full = TileRange{1, 0};
-  full.lo = __builtin_amdgcn_readfirstlane(full.lo);
-  full.hi = __builtin_amdgcn_readfirstlane(full.hi);
-
-  f32x16 dq[C::NDB];
-#pragma unroll
-  for (int db = 0; db < C::NDB; ++db) dq[db] = f32x16{};
-
-  // K / V tiles by LDS-DMA into the ring (as in the forward)
-  const GldsOff go_k = glds_offsets<SW_DUAL>(p.ldk, w, lane), go_v = glds_offsets<SW_ROW>(p.ldv, w, lane);
-  auto issue = [&](char* buf, long c0) {
-#pragma unroll
-    for (int sk = 0; sk < QT; ++sk) {
-      const long c = c0 + 64 * sk;
-      char* bk = buf + sk * C::NSUB * SUB;
-      char* bv = buf + (QT + sk) * C::NSUB * SUB;
-#pragma unroll
-      for (int sb = 0; sb < C::NSUB; ++sb) {
-        if (c + TL <= p.Lkv) {
-          tile_glds_fast(bk + sb * SUB, K + c * p.ldk + 64 * sb, go_k, w);
-          tile_glds_fast(bv + sb * SUB, V + c * p.ldv + 64 * sb, go_v, w);
-        } else {
-          tile_glds<SW_DUAL>(bk + sb * SUB, K + 64 * sb, p.ldk, c, p.Lkv, w, lane);
-          tile_glds<SW_ROW>(bv + sb * SUB, V + 64 * sb, p.ldv, c, p.Lkv, w, lane);
-        }
-      }
-    }
-  };
-  constexpr int OPS = 4 * QT * C::NSUB;  // 16-B LDS-DMA wave-instructions per tile per wave
-  auto wait_oldest = [&](int younger) {
-    if (younger > 0)
-      vmcnt<OPS>();
-    else
-      vmcnt<0>();
-  };
-#pragma unroll
-  for (int i = 0; i < NBUF - 1; ++i)
-    if (i < ntiles) issue(smem + i * BUF, kv_begin + (long)i * TLK);
-  wait_oldest(min(NBUF - 2, ntiles - 1));
-  OWLK_BARRIER();
-
-  for (int t = 0; t < ntiles; ++t) {
-    const long c0 = kv_begin + (long)t * TLK;
-    if (t + NBUF - 1 < ntiles) issue(smem + ((t + NBUF - 1) % NBUF) * BUF, c0 + (long)(NBUF - 1) * TLK);
-    const char* tb = smem + (t % NBUF) * BUF;
-    int kind = TILE_FULL;
-    if (t < full.lo || t >= full.hi) {
-      const long clast = (c0 + TLK - 1 < p.Lkv ? c0 + TLK - 1 : p.Lkv - 1);
-      kind = TILE_EMPTY;
-      if (wave_live) kind = classify(m, b, wfq0, wfq1, frame_of(m, c0), frame_of(m, clast));
-      if (kind == TILE_FULL && c0 + TLK > p.Lkv) kind = TILE_PARTIAL;
-    }
-    kind = __builtin_amdgcn_readfirstlane(kind);
-
-    if (kind != TILE_EMPTY) {
-      const bool masked = kind == TILE_PARTIAL;
-#pragma unroll
-      for (int sk = 0; sk < QT; ++sk) {
-      const char* lk = tb + sk * C::NSUB * SUB;
-      const char* lv = tb + (QT + sk) * C::NSUB * SUB;
-      unsigned long long bh = 0ull;
-      if (masked) bh = tile_bits(m, b, my_q, qok, c0 + 64 * sk, p.Lkv, true) >> (4 * h);
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-        f32x16 st = INIT ? sinit : f32x16{}, dp = INIT ? pinit : f32x16{};
-#pragma unroll
-        for (int s = 0; s < C::NS; ++s) {
-          st = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<SW_DUAL>(lk + (s >> 2) * SUB, 32 * kb, s & 3, lane),
-                                                       qf[s], st, 0, 0, 0);
-          dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(frag_row<SW_ROW>(lv + (s >> 2) * SUB, 32 * kb, s & 3, lane),
-                                                       df[s], dp, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          st[r] = INIT ? __builtin_amdgcn_exp2f(st[r]) : __builtin_amdgcn_exp2f(fmaf(st[r], p.scale_log2, -L2));
-        if (masked) {
-          if (kb == 0)
-            apply_bits<0>(st, bh, 0.f);
-          else
-            apply_bits<32>(st, bh, 0.f);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) dp[r] = INIT ? st[r] * dp[r] : st[r] * (dp[r] - Dl);
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const bf16x8 sf = acc_frag(dp, s);
-#pragma unroll
-          for (int db = 0; db < C::NDB; ++db)
-            dq[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                frag_tr<SW_DUAL>(lk + (db >> 1) * SUB, 32 * kb, s, db & 1, lane), sf, dq[db], 0, 0, 0);
-        }
-      }
-      }  // sk
-    }
-    wait_oldest(min(NBUF - 2, ntiles - 2 - t));
-    OWLK_BARRIER();
-  }
-  if (qok) store_rowT<C::NDB>(p.dq + b * p.sdqb + my_q * p.lddq + head * D, dq, p.scale, h);
-}
-
 // ======================================================================== dQ on 16x16x32 MFMAs
-// attn_bwd_dq_k (D 64, accumulator-init form) with every product on v_mfma_f32_16x16x32_bf16
-// (see attn_bwd_dkdv16_k): per wave 32 queries as two 16-query column tiles (lane column c), per
-// 32-key block two 16-row key tiles; S and dP take K / V rows from LDS as A and q' = bf16(c q) /
-// dO from registers as B, so their accumulators (key on rows 4 g + r) are the B operands of
-// dQ^T += K^T dS in the permuted key order, K^T read by two ds_read_b64_tr_b16 per fragment.
+// Workgroup = 4 waves x 16 NT queries, listed from the last query block down (longest sweeps first);
+// sweeps key tiles of QT x 64 rows through the K / V ring, every product on v_mfma_f32_16x16x32_bf16
+// (see attn_bwd_dkdv16_k): per wave NT 16-query column tiles (lane column c), per 32-key block two
+// 16-row key tiles; S and dP take K / V rows from LDS as A and q' = bf16(c q) / dO from registers as
+// B.  Row constants ride in the accumulators: the S and dP chains start from -lse2 and -delta, so S
+// arrives as the exp2 argument and dP - delta needs no subtraction.  The S / dP accumulators (key on
+// rows 4 g + r) are the B operands of dQ^T += K^T dS in the permuted key order, K^T read by two
+// ds_read_b64_tr_b16 per fragment.  QT = 2 (long sweeps at D 64; two-slot ring) pays the per-tile
+// fixed costs once per two 64-key tiles, as in the dK/dV kernels.
 // D 128 (dit_v4_5B): two 64-column LDS sub-tiles per K / V tile, QT = 1 with a two-slot ring
 // (64 KiB per workgroup, two workgroups per CU).
 // NT 16-query column tiles per wave (2: 32 queries, 3: 48): with 48, every K / V fragment read from
@@ -1069,76 +895,44 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq16_k(BwdP p) {
 
 // 128-row swept tiles (QT 2) pay the per-tile fixed costs once per two 64-row tiles; windowed sweeps
 // that are only a few tiles long lose more to their doubled mask-edge tiles (window 16 x 64 tokens:
-// +60 %), so QT 2 is taken for unwindowed masks and for windows of at least OWLK_BWD_QT2_MIN tokens
-// (default 4096: mmdit_v2's 256-frame layers)
-static bool long_sweep(const MaskP& m) {
-  static const long qt2_min = getenv("OWLK_BWD_QT2_MIN") ? atol(getenv("OWLK_BWD_QT2_MIN")) : 4096;
-  return m.window <= 0 || (long)m.window * m.tpf >= qt2_min;
-}
+// +60 %), so the D 64 kernels take QT 2 for unwindowed masks and for windows of at least 4096 tokens
+// (mmdit_v2's 256-frame layers)
+static bool long_sweep(const MaskP& m) { return m.window <= 0 || (long)m.window * m.tpf >= 4096; }
 
 template <int D>
 int launch_bwd(int phases, const BwdP& p, long B, int H, long Lq, long Lkv, hipStream_t s) {
   if (phases & 1) {
     const dim3 grid((unsigned)((Lkv + TB - 1) / TB), (unsigned)H, (unsigned)B);
     if constexpr (D == 64) {
-      // the 16x16x32-MFMA variant by default (OWLK_DKDV16 = 0: 32x32x16): -7 % at the dit_v4 shape
-      static const int v16 = getenv("OWLK_DKDV16") ? atoi(getenv("OWLK_DKDV16")) : 1;
-      if (v16) {
-        if (long_sweep(p.m))
-          hipLaunchKernelGGL((attn_bwd_dkdv16_k<2>), grid, dim3(256), 0, s, p);
-        else
-          hipLaunchKernelGGL((attn_bwd_dkdv16_k<1>), grid, dim3(256), 0, s, p);
-      } else if (p.m.window <= 0) {
-        hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 2>), grid, dim3(256), 0, s, p);
-      } else {
-        hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 1>), grid, dim3(256), 0, s, p);
-      }
+      if (long_sweep(p.m))
+        hipLaunchKernelGGL((attn_bwd_dkdv16_k<2>), grid, dim3(256), 0, s, p);
+      else
+        hipLaunchKernelGGL((attn_bwd_dkdv16_k<1>), grid, dim3(256), 0, s, p);
     } else {
-      // D 128 (one wave per SIMD): OWLK_DKDV128 = 0 plain, 1 pipelined FULL tiles, 2 128-row
-      // query tiles (two-slot ring, 130 KiB), 3 both (default; global 134.7 -> 99.6 ms, local
-      // 3.24 -> 2.70 ms at 20 heads x 98,304 tokens)
-      static const int v128 = getenv("OWLK_DKDV128") ? atoi(getenv("OWLK_DKDV128")) : 3;
-      const int v = p.m.window <= 0 ? v128 : (v128 & 1);
-      if (v == 3)
-        hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 2, true>), grid, dim3(256), 0, s, p);
-      else if (v == 2)
-        hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 2, false>), grid, dim3(256), 0, s, p);
-      else if (v == 1)
-        hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 1, true>), grid, dim3(256), 0, s, p);
+      // 128-row query tiles (two-slot ring, 130 KiB) without a window: global 134.7 -> 99.6 ms with
+      // the pipelined FULL tiles at 20 heads x 98,304 tokens (local 3.24 -> 2.70 ms)
+      if (p.m.window <= 0)
+        hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 2>), grid, dim3(256), 0, s, p);
       else
         hipLaunchKernelGGL((attn_bwd_dkdv_k<D, 1>), grid, dim3(256), 0, s, p);
     }
     if (int e = owlk::check_launch("attn_bwd_dkdv")) return e;
   }
   if (phases & 2) {
-    const dim3 grid((unsigned)((Lq + TB - 1) / TB), (unsigned)H, (unsigned)B);
     if constexpr (D == 64) {
-      static const int v16 = getenv("OWLK_DQ16") ? atoi(getenv("OWLK_DQ16")) : 1;  // 16x16x32 variant (0: 32x32x16)
       // long sweeps: 48 queries per wave (3 x 16-query tiles, 192 per workgroup): global dQ 36.7 ->
-      // 34.2 ms at the dit_v4 shape; window 16 keeps 32 (1.07 -> 1.13 ms with 48).  OWLK_DQ_NT = 2
-      // forces 32 everywhere.
-      static const int nt = getenv("OWLK_DQ_NT") ? atoi(getenv("OWLK_DQ_NT")) : 3;
-      const dim3 grid3((unsigned)((Lq + 191) / 192), (unsigned)H, (unsigned)B);
-      if (v16 && nt == 3 && long_sweep(p.m)) {
-        hipLaunchKernelGGL((attn_bwd_dq16_k<64, 2, 3>), grid3, dim3(256), 0, s, p);
-      } else if (v16) {
-        if (long_sweep(p.m))
-          hipLaunchKernelGGL((attn_bwd_dq16_k<64, 2>), grid, dim3(256), 0, s, p);
-        else
-          hipLaunchKernelGGL((attn_bwd_dq16_k<64, 1>), grid, dim3(256), 0, s, p);
-      } else if (p.m.window <= 0) {
-        hipLaunchKernelGGL((attn_bwd_dq_k<D, 2>), grid, dim3(256), 0, s, p);
+      // 34.2 ms at the dit_v4 shape; window 16 keeps 32 (1.07 -> 1.13 ms with 48)
+      if (long_sweep(p.m)) {
+        const dim3 grid((unsigned)((Lq + 191) / 192), (unsigned)H, (unsigned)B);
+        hipLaunchKernelGGL((attn_bwd_dq16_k<64, 2, 3>), grid, dim3(256), 0, s, p);
       } else {
-        hipLaunchKernelGGL((attn_bwd_dq_k<D, 1>), grid, dim3(256), 0, s, p);
+        const dim3 grid((unsigned)((Lq + TB - 1) / TB), (unsigned)H, (unsigned)B);
+        hipLaunchKernelGGL((attn_bwd_dq16_k<64, 1>), grid, dim3(256), 0, s, p);
       }
     } else {
-      // D 128: the 16x16x32 form (32 queries per wave, two waves per SIMD) by default;
-      // OWLK_DQ16_128 = 0 the 32x32x16 attn_bwd_dq_k
-      static const int v16 = getenv("OWLK_DQ16_128") ? atoi(getenv("OWLK_DQ16_128")) : 1;
-      if (v16)
-        hipLaunchKernelGGL((attn_bwd_dq16_k<128, 1>), grid, dim3(256), 0, s, p);
-      else
-        hipLaunchKernelGGL((attn_bwd_dq_k<D, 1>), grid, dim3(256), 0, s, p);
+      // 32 queries per wave, two waves per SIMD
+      const dim3 grid((unsigned)((Lq + TB - 1) / TB), (unsigned)H, (unsigned)B);
+      hipLaunchKernelGGL((attn_bwd_dq16_k<128, 1>), grid, dim3(256), 0, s, p);
     }
     if (int e = owlk::check_launch("attn_bwd_dq")) return e;
   }

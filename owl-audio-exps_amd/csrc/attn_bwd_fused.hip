@@ -53,23 +53,12 @@
 #ifndef OWLK_FUSED_PROF
 #define OWLK_FUSED_PROF 0
 #endif
-// software-pipeline depth of the 32x32 dQ products (k-steps of reads in flight ahead of the MFMA)
-// values formed from an opaque lane id at each use instead of kept across the sweep (bits: 1 the
-// ring's DMA offsets, 2 the dS image addresses, 4 the operand read addresses, 8 the mask rows and
-// the epilogue's keys); 0 = all kept (hipcc spills some of them)
-#ifndef OWLK_FUSED_REMAT
-#define OWLK_FUSED_REMAT 0
-#endif
-#ifndef OWLK_FUSED_KV_STAGE  // 1: dK / dV stored as whole rows through LDS
-#define OWLK_FUSED_KV_STAGE 1
-#endif
-#ifndef OWLK_FUSED_DEQ_PF  // 1: an item's successor is claimed during its epilogue
-#define OWLK_FUSED_DEQ_PF 1
-#endif
-#ifndef OWLK_FUSED_DQ_PF
-#define OWLK_FUSED_DQ_PF 3
-#endif
-#ifndef OWLK_FUSED_DMA47  // 1: the ring's LDS-DMA is issued by waves 4-7 only (no dQ work), 0: by all 8
+// software-pipeline depth of the dQ products: k-steps of operand reads in flight ahead of the MFMA
+constexpr int DQ_PF = 3;
+// 1: the ring's LDS-DMA is issued by waves 4-7 only (no dQ work), 0: by all 8 (the old split, slower:
+// profiles/r5d_dma47_ab.txt).  The 0 form stays in the source only because hipcc orders the prologue
+// of attn_bwd_fused_k differently once its (unused) per-lane offsets drow / dch are gone
+#ifndef OWLK_FUSED_DMA47
 #define OWLK_FUSED_DMA47 1
 #endif
 
@@ -123,13 +112,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
   // wave-instruction, swizzled source chunk)
   const int drow = 8 * w + (lane >> 3);
   const int dch = (lane & 7) ^ swz_ring(drow);
-  // (formed from an opaque lane id at each use: kept live across the sweep they were spilled, and
-  // each reload's vmcnt(0) drained the dQ stores before the ring's DMA)
   // OWLK_FUSED_DMA47: waves 4-7 move rows 16 (w - 4) + 8 h + (lane >> 3) instead (h = 0, 1)
   auto row_off = [&](int ld, int h = 0) {
-    const int ln = (int)opaque<1>((unsigned)lane);
-    const int r = OWLK_FUSED_DMA47 ? 16 * (w - 4) + 8 * h + (ln >> 3) : 8 * w + (ln >> 3);
-    return (unsigned)((r * ld + (((ln & 7) ^ swz_ring(r)) * 8)) * 2);
+    const int r = OWLK_FUSED_DMA47 ? 16 * (w - 4) + 8 * h + (lane >> 3) : 8 * w + (lane >> 3);
+    return (unsigned)((r * ld + (((lane & 7) ^ swz_ring(r)) * 8)) * 2);
   };
 
   // OWLK_FUSED_PROF: per-step phases {dq, main, vmwait, barrier} and per-item {dequeue, prologue,
@@ -161,17 +147,11 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
       item_of(x, __hip_atomic_fetch_add(p.hdr + x, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), chain, jj);
     }
   };
-  if (OWLK_FUSED_DEQ_PF && threadIdx.x == 0) claim(0, sh_item[0], sh_item[1]);
+  if (threadIdx.x == 0) claim(0, sh_item[0], sh_item[1]);
   for (;;) {
     const unsigned long long ca = OWLK_FUSED_PROF ? __builtin_amdgcn_s_memtime() : 0ull;
-    // ---- dequeue: the next item of this XCD's queue (others' when it is empty, unless local);
-    // OWLK_FUSED_DEQ_PF: claimed during the previous item's epilogue
-    if (!OWLK_FUSED_DEQ_PF && threadIdx.x == 0) {
-      int chain, jj;
-      claim(0, chain, jj);
-      sh_item[0] = chain;
-      sh_item[1] = jj;
-    }
+    // ---- dequeue: the next item of this XCD's queue (others' when it is empty, unless local),
+    // claimed during the previous item's epilogue
     __syncthreads();
     const int chain = __builtin_amdgcn_readfirstlane(sh_item[0]);
     const int j = __builtin_amdgcn_readfirstlane(sh_item[1]);
@@ -381,7 +361,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
 
     // dQ^T[32 d x 32 q] of tile i += K^T[32 d x 16 keys] dS^T[16 keys x 32 q] over the item's keys,
     // from the K image and the tile's dS image (written in the tile's own step); both fragments in
-    // frag_tr's permuted row order (the same for A and B), software-pipelined OWLK_FUSED_DQ_PF
+    // frag_tr's permuted row order (the same for A and B), software-pipelined DQ_PF
     // k-steps deep
     auto dq_mfma = [&](int i) {
       if constexpr (counting) {
@@ -396,7 +376,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
       if constexpr (DQ16) {
         // dQ^T[16 d x 16 q] (two query tiles) += K^T[16 d x 32 keys] dS^T[32 keys x 16 q]: frag_tr16 at
         // row0 = 32 kk (immediate kk * 4 KiB, + 2 KiB for the second 4-row group), pipelined as below
-        constexpr int NK = FKB / 32, PF = OWLK_FUSED_DQ_PF;
+        constexpr int NK = FKB / 32, PF = DQ_PF;
         const unsigned sb0 = lds_addr(smem + DS_OFF + (i & 1) * DS_BYTES);
         const unsigned ka = lds_addr(kimg) + offk, s0 = sb0 + offs0, s1 = sb0 + offs1;
         s16x4 r[PF + 1][6];
@@ -421,7 +401,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
         });
         return;
       }
-      constexpr int NK = FKB / 16, PF = OWLK_FUSED_DQ_PF;
+      constexpr int NK = FKB / 16, PF = DQ_PF;
       const unsigned kb0 = lds_addr(kimg), sb0 = lds_addr(smem + DS_OFF + (i & 1) * DS_BYTES);
       const unsigned ka = kb0 + ok32a, kb = kb0 + ok32b, sa = sb0 + os32a, sb = sb0 + os32b;
       s16x4 r[PF + 1][4];
@@ -505,7 +485,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
       // a tile's S / dP operands of query rows 32 qb .. + 31 (lse2, delta rows, Q and dO
       // fragments), by asm in the order they are consumed: 12 LDS reads
       const unsigned sbase = lds_addr(smem + (t & 1) * RING_SLOT);
-      const unsigned a_r0 = sbase + opaque<4>(ro0), a_r1 = sbase + opaque<4>(ro1), a_l = sbase + 16 * (opaque<4>((unsigned)lane) >> 4);
+      const unsigned a_r0 = sbase + ro0, a_r1 = sbase + ro1, a_l = sbase + 16 * ((unsigned)lane >> 4);
       f32x4 lr[2], dr[2];
       bf16x8 aq[2][2], ad[2][2];  // [k step][16-row query tile]
       auto issue_a = [&](auto qbc) {
@@ -541,14 +521,13 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
 
       const unsigned dsw = lds_addr(smem + DS_OFF + (t & 1) * DS_BYTES) + dsl;
       auto ds_put = [&](int t2, int qb, int e, bf16x4 v) {
-        *(AS3 bf16x4*)(uintptr_t)(dsw + 2048 * t2 + ((unsigned)(64 * qb + 32 * e) ^ opaque<2>(dsx))) = v;
+        *(AS3 bf16x4*)(uintptr_t)(dsw + 2048 * t2 + ((unsigned)(64 * qb + 32 * e) ^ dsx)) = v;
       };
       unsigned bh[2] = {0u, 0u};  // bit 4 m + r: query row q0 + 16 m + 4 g + r of key t2
       if (masked) {  // query rows [frame(key) tpf, L) (causal) / [0, L) of the tile, per key
 #pragma unroll
         for (int t2 = 0; t2 < 2; ++t2) {
-          // the key from an opaque lane id: its row range is formed here, not kept across the sweep
-          const int k = kw0 + 16 * t2 + (int)(opaque<8>((unsigned)lane) & 15), fk = frame(p, k);
+          const int k = my_k[t2], fk = frame(p, k);
           const int lo = q_lo_frame(p, fk) * p.tpf - q0, hi = (RUNS ? khi[t2] : (int)q_hi_end(p, fk)) - q0;
           const unsigned long long b64 = k < L ? range_bits(lo, hi) >> (4 * g) : 0ull;
           bh[t2] = (unsigned)(b64 & 0xF) | (unsigned)((b64 >> 12) & 0xF0) | (unsigned)((b64 >> 24) & 0xF00) |
@@ -594,10 +573,10 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
             tq[ds][2] = tr_rd<128 * 32 * qb>(a);
             tq[ds][3] = tr_rd<128 * 32 * qb + 2048>(a);
           };
-          rd_t(std::integral_constant<int, 0>{}, sbase + opaque<4>(tro0));
-          rd_t(std::integral_constant<int, 1>{}, sbase + opaque<4>(tro1));
-          rd_t(std::integral_constant<int, 2>{}, sbase + opaque<4>(tro2));
-          rd_t(std::integral_constant<int, 3>{}, sbase + opaque<4>(tro3));
+          rd_t(std::integral_constant<int, 0>{}, sbase + tro0);
+          rd_t(std::integral_constant<int, 1>{}, sbase + tro1);
+          rd_t(std::integral_constant<int, 2>{}, sbase + tro2);
+          rd_t(std::integral_constant<int, 3>{}, sbase + tro3);
 #pragma unroll
           for (int qs = 0; qs < 2; ++qs)
 #pragma unroll
@@ -678,7 +657,7 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
     if (dq_epi) dq_begin(t_lo);
     // the next item's claim on this XCD's queue: its return is waited for with the dQ stores
     int npf = 0;
-    if (OWLK_FUSED_DEQ_PF && threadIdx.x == 0)
+    if (threadIdx.x == 0)
       npf = __hip_atomic_fetch_add(p.hdr + xcc, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (dq_epi) {
       dq_mfma(t_lo);
@@ -688,15 +667,12 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
     __syncthreads();  // also: every wave is done with the LDS before the next item's DMA
     if (threadIdx.x == 0) {
       __hip_atomic_store(flg + t_lo * FLAG_STRIDE, j + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (OWLK_FUSED_DEQ_PF) {
-        int nc = -1, nj = 0;
-        if (!item_of((int)xcc, npf, nc, nj)) claim(1, nc, nj);
-        sh_item[0] = nc;  // read after the next item's first barrier
-        sh_item[1] = nj;
-      }
+      int nc = -1, nj = 0;
+      if (!item_of((int)xcc, npf, nc, nj)) claim(1, nc, nj);
+      sh_item[0] = nc;  // read after the next item's first barrier
+      sh_item[1] = nj;
     }
 
-#if OWLK_FUSED_KV_STAGE
     // dK, dV through this wave's 8 KiB of the (now free) dS images, stored as whole 128-B rows with
     // 16-B stores (lane-held 8-B pieces were 16 stores per lane, whose tail the next item's
     // prologue waits for: vmcnt counts stores).  Row r = key kw0 + r, 16-B chunk x at x ^ (r & 7)
@@ -730,27 +706,6 @@ __global__ __launch_bounds__(512, 2) void attn_bwd_fused_k(FusedP p) {
         }
       }
     }
-#else
-    // dK[key][d], dV[key][d]: this lane holds d = 16 ds + 4 g + r of its two keys
-#pragma unroll
-    for (int t2 = 0; t2 < 2; ++t2) {
-      const int k = kw0 + 16 * t2 + (int)(opaque<8>((unsigned)lane) & 15);
-      if (k >= L) continue;
-      bf16* pk = p.dk + b * p.sdkb + (long)k * p.lddk + head * 64 + 4 * g;
-      bf16* pv = p.dv + b * p.sdvb + (long)k * p.lddv + head * 64 + 4 * g;
-#pragma unroll
-      for (int ds = 0; ds < 4; ++ds) {
-        bf16x4 a4, b4;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          a4[e] = (bf16)(dk[ds][t2][e] * -p.scale);  // dS was accumulated negated
-          b4[e] = (bf16)dv[ds][t2][e];
-        }
-        *(bf16x4*)(pk + 16 * ds) = a4;
-        *(bf16x4*)(pv + 16 * ds) = b4;
-      }
-    }
-#endif
     if (OWLK_FUSED_PROF) {
       const unsigned long long ce = __builtin_amdgcn_s_memtime();
       prof[4] += cb - ca;

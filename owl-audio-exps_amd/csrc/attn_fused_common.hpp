@@ -8,12 +8,6 @@
 
 #define AS1 __attribute__((address_space(1)))
 #define AS3 __attribute__((address_space(3)))
-#ifndef OWLK_FUSED_REMAT
-#define OWLK_FUSED_REMAT 0
-#endif
-#ifndef OWLK_FUSED_DQ_PF
-#define OWLK_FUSED_DQ_PF 3
-#endif
 
 namespace owlk_fused {
 
@@ -35,7 +29,9 @@ constexpr int FLAG_STRIDE = 16;                // ints: one 64-B line per query-
 constexpr long HDR_BYTES = 256;  // [0, 8) dequeue counters, [8] error word, [9] keys per item
 constexpr int ACC_TILE_BYTES = FQT * 64 * 4;   // fp32 accumulator of one query tile
 // dQ^T products: 0 = 32x32x16 MFMAs on waves 0-3 (one 32 d x 32 q tile each); 1 = 16x16x32 MFMAs
-// on all 8 waves (one 16 d x 32 q quarter each: 50 % more LDS bytes, no idle waves)
+// on all 8 waves (one 16 d x 32 q quarter each: 50 % more LDS bytes, no idle waves; measured and
+// rejected).  The 1 form stays in the source only because hipcc orders the prologue of
+// attn_bwd_fused_k differently once its (unused) per-lane offsets offk / offs0 / offs1 are gone
 #ifndef OWLK_FUSED_DQ16
 #define OWLK_FUSED_DQ16 0
 #endif
@@ -164,13 +160,6 @@ DEV void dma4_sc1(unsigned lds, const void* base, unsigned off) {
                : "memory", "m0");
 }
 #pragma clang diagnostic pop
-// a copy the compiler cannot see through: values formed from it are formed where they are used
-// (hoisted out of the sweep, the dS image's 16 per-lane piece addresses were kept live and spilled)
-template <int BIT = 0>
-DEV unsigned opaque(unsigned x) {
-  if (!BIT || (OWLK_FUSED_REMAT & BIT)) asm volatile("" : "+v"(x));
-  return x;
-}
 template <int N>
 DEV void vm_wait() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");

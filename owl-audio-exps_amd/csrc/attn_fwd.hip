@@ -5,7 +5,11 @@
 // allowed keys of attn_common.hpp, bf16 in / fp32 accumulate / bf16 out, plus the per-row
 // log-sum-exp in base 2 (lse2 = natural lse / ln 2, include/owlk.h) for the backward pass.
 //
-// Workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 rows.  Per 64-key
+// Kernels (launch_fwd picks): attn_fwd16_k, the bounded softmax on 16x16x32 MFMAs (training shapes);
+// attn_fwd16_split_k / attn_decode_joint_k (decode); attn_fwd_k (D 128) / attn_fwd2_k (D 64), the
+// running-max softmax on 32x32x16 MFMAs for callers without a score bound.  The common scheme, as
+// attn_fwd_k has it:
+// workgroup = 4 waves = 128 query rows of one (batch, head); each wave owns 32 rows.  Per 64-key
 // tile the wave computes S^T = K Q^T with v_mfma_f32_32x32x16_bf16 (key rows in registers, the
 // query on the lane) so the softmax row statistics stay in-lane (+ one lane^32 exchange), then
 // feeds the S^T accumulators straight back as the B operand of O^T += V^T P^T (V^T fragments
@@ -45,7 +49,7 @@ struct FwdP {
   long Lq, Lkv;
   int H;
   float scale_log2;     // softmax scale * log2(e)
-  float bound;          // BOUNDED: |q.k| <= bound for every pair (raw score units)
+  float bound;          // > 0: |q.k| <= bound for every pair (raw score units); 0: no bound known
   MaskP m;
 };
 
@@ -54,12 +58,13 @@ DEV void vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// BOUNDED = true: the caller guarantees |q.k| <= p.bound (QK-RMSNorm'd q, k have |q| = |k| =
-// sqrt(D), attn.py:84), so every exp2 argument c*s lies in [-c*bound, c*bound] (+-11.8 at D 64):
-// p = exp2(c s) needs no running max, no offset and no rescale.  Softmax is shift-invariant, so
-// the result is the same function; P keeps bf16's relative precision at any magnitude.
-template <int D, bool BOUNDED>
+// Running-max softmax on 32x32x16 MFMAs: the score_bound = 0 path at D 128 (no bound on |q.k| is
+// known, so the exp2 arguments are offset by the row maximum and l / O rescaled when it moves).
+// The bounded-softmax kernels (attn_fwd16_k and the decode kernels below, attn_fwd4.hip) need none of
+// that; production runs those, the tests use this path as an independent forward.
+template <int D>
 __global__ __launch_bounds__(256) void attn_fwd_k(FwdP p) {
+  static_assert(D == 128, "attn_fwd_k is built for head_dim 128 only (D 64: attn_fwd2_k)");
   using C = Cfg<D>;
   // ONE __shared__ object (the reduction slot sits past the ring): with a second one hipcc tags
   // the LDS-DMA with an alias scope and drains the ring (vmcnt(0)) before the first ds_read of
@@ -108,19 +113,6 @@ __global__ __launch_bounds__(256) void attn_fwd_k(FwdP p) {
 #pragma unroll
   for (int s = 0; s < C::NS; ++s)
     qf[s] = my_q < p.Lq ? *(const bf16x8*)(Q + my_q * p.ldq + 16 * s + 8 * h) : bf16x8{};
-  if constexpr (BOUNDED) {
-    // q' = bf16(q * c), c = scale * log2(e): S' = K q'^T is already the exp2 argument.  With
-    // |q.k| <= bound, |S'| <= c * bound (checked on the host), so p = exp2(S') needs no running
-    // max and no offset; the one extra rounding of q' is 2^-9 relative per element.
-#pragma unroll
-    for (int s = 0; s < C::NS; ++s) {
-      float f[8];
-      unpack8(qf[s], f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) f[j] *= p.scale_log2;
-      qf[s] = pack8(f);
-    }
-  }
   const long wlast = (r0 + 31 < p.Lq ? r0 + 31 : p.Lq - 1);
   const bool wave_live = r0 < p.Lq;
   const int wfq0 = frame_of(m, r0 + m.q_offset), wfq1 = frame_of(m, wlast + m.q_offset);
@@ -132,7 +124,7 @@ __global__ __launch_bounds__(256) void attn_fwd_k(FwdP p) {
   f32x16 o[C::NDB];
 #pragma unroll
   for (int db = 0; db < C::NDB; ++db) o[db] = f32x16{};
-  float mrow = BOUNDED ? 0.f : -INFINITY, lrow = 0.f;
+  float mrow = -INFINITY, lrow = 0.f;
 
   // ---- K / V tiles by LDS-DMA into a C::NBUF-deep ring, C::NBUF - 1 tiles in flight; per-lane
   // source offsets hoisted (wave-uniform tile bases), per-lane clamping only on the ragged tail
@@ -198,34 +190,30 @@ __global__ __launch_bounds__(256) void attn_fwd_k(FwdP p) {
         apply_bits<0>(st[0], bh, -INFINITY);
         apply_bits<32>(st[1], bh, -INFINITY);
       }
-      float mc = 0.f;
-      if constexpr (!BOUNDED) {
-        // row max on raw scores; p = exp2(s * c - m * c) is one FMA + one v_exp per score
-        float tmax = -INFINITY;
+      // row max on raw scores; p = exp2(s * c - m * c) is one FMA + one v_exp per score
+      float tmax = -INFINITY;
 #pragma unroll
-        for (int kb = 0; kb < 2; ++kb)
+      for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[kb][r]);
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float mnew = fmaxf(mrow, tmax);
-        mc = mnew == -INFINITY ? 0.f : mnew * p.scale_log2;
-        if (__any(mnew > mrow)) {  // some row's max moved: rescale l and O (exactly)
-          const float alpha = __builtin_amdgcn_exp2f(mrow * p.scale_log2 - mc);
-          lrow *= alpha;
+        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[kb][r]);
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+      const float mnew = fmaxf(mrow, tmax);
+      const float mc = mnew == -INFINITY ? 0.f : mnew * p.scale_log2;
+      if (__any(mnew > mrow)) {  // some row's max moved: rescale l and O (exactly)
+        const float alpha = __builtin_amdgcn_exp2f(mrow * p.scale_log2 - mc);
+        lrow *= alpha;
 #pragma unroll
-          for (int db = 0; db < C::NDB; ++db)
+        for (int db = 0; db < C::NDB; ++db)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-        }
-        mrow = mnew;
+          for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
       }
+      mrow = mnew;
       float psum = 0.f;
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const float pv = BOUNDED ? __builtin_amdgcn_exp2f(st[kb][r])
-                                   : __builtin_amdgcn_exp2f(fmaf(st[kb][r], p.scale_log2, -mc));
+          const float pv = __builtin_amdgcn_exp2f(fmaf(st[kb][r], p.scale_log2, -mc));
           st[kb][r] = pv;
           psum += pv;
         }
@@ -270,8 +258,8 @@ __global__ __launch_bounds__(256) void attn_fwd_k(FwdP p) {
 // and every V^T fragment (ds_read_b64_tr_b16) read from LDS feeds two MFMAs, and the per-tile
 // fixed costs (DMA issue, ring bookkeeping, classification, barrier) are paid once per 32
 // MFMAs instead of 16.  Workgroup = 4 waves = 256 query rows; ~200 VGPRs -> 2 waves per SIMD.
+// Running-max softmax as attn_fwd_k: the score_bound = 0 path at D 64.
 constexpr int QT2 = 256;
-template <bool BOUNDED>
 __global__ __launch_bounds__(256, 2) void attn_fwd2_k(FwdP p) {
   using C = Cfg<64>;
   __shared__ __attribute__((aligned(16))) char smem[C::NBUF * C::TILEB + 16];
@@ -320,16 +308,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_k(FwdP p) {
 #pragma unroll
     for (int s = 0; s < 4; ++s)
       qf[qb][s] = my_q[qb] < p.Lq ? *(const bf16x8*)(Q + my_q[qb] * p.ldq + 16 * s + 8 * h) : bf16x8{};
-    if constexpr (BOUNDED) {  // q' = bf16(q c): see attn_fwd_k
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        float f[8];
-        unpack8(qf[qb][s], f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f[j] *= p.scale_log2;
-        qf[qb][s] = pack8(f);
-      }
-    }
   }
   const long wlast = (r0 + 63 < p.Lq ? r0 + 63 : p.Lq - 1);
   const bool wave_live = r0 < p.Lq;
@@ -342,7 +320,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_k(FwdP p) {
   f32x16 o[2][2];
 #pragma unroll
   for (int qb = 0; qb < 2; ++qb) o[qb][0] = o[qb][1] = f32x16{};
-  float mrow[2] = {BOUNDED ? 0.f : -INFINITY, BOUNDED ? 0.f : -INFINITY}, lrow[2] = {0.f, 0.f};
+  float mrow[2] = {-INFINITY, -INFINITY}, lrow[2] = {0.f, 0.f};
 
   const GldsOff goff_k = glds_offsets<SW_ROW>(p.ldk, w, lane), goff_v = glds_offsets<SW_TR>(p.ldv, w, lane);
   auto issue = [&](char* buf, long c0) {
@@ -408,34 +386,30 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_k(FwdP p) {
       }
 #pragma unroll
       for (int qb = 0; qb < 2; ++qb) {
-        float mc = 0.f;
-        if constexpr (!BOUNDED) {
-          float tmax = -INFINITY;
+        float tmax = -INFINITY;
 #pragma unroll
-          for (int kb = 0; kb < 2; ++kb)
+        for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[kb][qb][r]);
-          tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-          const float mnew = fmaxf(mrow[qb], tmax);
-          mc = mnew == -INFINITY ? 0.f : mnew * p.scale_log2;
-          if (__any(mnew > mrow[qb])) {
-            const float alpha = __builtin_amdgcn_exp2f(mrow[qb] * p.scale_log2 - mc);
-            lrow[qb] *= alpha;
+          for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st[kb][qb][r]);
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        const float mnew = fmaxf(mrow[qb], tmax);
+        const float mc = mnew == -INFINITY ? 0.f : mnew * p.scale_log2;
+        if (__any(mnew > mrow[qb])) {
+          const float alpha = __builtin_amdgcn_exp2f(mrow[qb] * p.scale_log2 - mc);
+          lrow[qb] *= alpha;
 #pragma unroll
-            for (int db = 0; db < 2; ++db)
+          for (int db = 0; db < 2; ++db)
 #pragma unroll
-              for (int r = 0; r < 16; ++r) o[qb][db][r] *= alpha;
-          }
-          mrow[qb] = mnew;
+            for (int r = 0; r < 16; ++r) o[qb][db][r] *= alpha;
         }
+        mrow[qb] = mnew;
         // row sums in four independent partial sums (no 32-long dependent add chain)
         float ps[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const float pv = BOUNDED ? __builtin_amdgcn_exp2f(st[kb][qb][r])
-                                     : __builtin_amdgcn_exp2f(fmaf(st[kb][qb][r], p.scale_log2, -mc));
+            const float pv = __builtin_amdgcn_exp2f(fmaf(st[kb][qb][r], p.scale_log2, -mc));
             st[kb][qb][r] = pv;
             ps[r & 3] += pv;
           }
@@ -482,13 +456,18 @@ __global__ __launch_bounds__(256, 2) void attn_fwd2_k(FwdP p) {
 }
 
 // Bounded softmax, every product on v_mfma_f32_16x16x32_bf16 (the chip holds a higher clock on
-// that shape: MI355X_MICROARCH.md, DVFS give-back item 7).  A wave owns NQ 16-query column tiles
+// that shape: MI355X_MICROARCH.md, DVFS give-back item 7).  The caller guarantees |q.k| <= p.bound
+// (QK-RMSNorm'd q, k have |q| = |k| = sqrt(D), attn.py:84), so with q' = bf16(c q), c = scale *
+// log2(e), S' = K q'^T is already the exp2 argument and lies in [-c bound, c bound] (+-11.8 at D 64,
+// checked on the host): p = exp2(S') needs no running max, no offset and no rescale.  Softmax is
+// shift-invariant, so the result is the same function; P keeps bf16's relative precision at any
+// magnitude, and the one extra rounding of q' is 2^-9 relative per element.  A wave owns NQ 16-query column tiles
 // (lane column c = lane & 15; NQ = 4 at D 64, 2 at D 128 so O^T and q' fit two waves per SIMD) and
 // sweeps 64-key tiles as four 16-key row tiles: S^T[key][q] = K q'^T with K rows from LDS (A) and
 // q' = bf16(c q) in registers (B), so a query's scores sit in column c, rows 4 g + r (g = lane >> 4);
 // P feeds O^T += V^T P as the B operand in the permuted key order (pack_perm), V^T read by
-// frag_tr16.  Row sums stay per lane group until the epilogue (4 partial sums per query, added
-// across the groups there).  D 128 = two 64-column LDS sub-tiles per K / V tile.
+// frag_tr16.  Row sums are one more MFMA per query tile and 32-key part (ones^T P: every accumulator
+// row holds the query's sum).  D 128 = two 64-column LDS sub-tiles per K / V tile.
 template <int D, int NQ_ = D == 64 ? 4 : 2>
 struct F16Cfg {
   static constexpr int NQ = NQ_;              // 16-query tiles per wave
@@ -498,10 +477,7 @@ struct F16Cfg {
 };
 // KTT keys per swept tile: 64, or 128 (D 64 long sweeps: a two-slot ring of 32 KiB tiles, the
 // per-tile fixed costs paid once per 144 MFMAs)
-#ifndef OWLK_FWD_STAGE  // 1: D = 64 output rows stored whole through LDS
-#define OWLK_FWD_STAGE 1
-#endif
-template <int D, bool RS, int KTT = KT, int NQ = F16Cfg<D>::NQ>
+template <int D, int KTT = KT, int NQ = F16Cfg<D>::NQ>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_k(FwdP p) {
   using C = Cfg<D>;
   using F = F16Cfg<D, NQ>;
@@ -594,12 +570,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_k(FwdP p) {
   for (int ds = 0; ds < F::NDS; ++ds)
 #pragma unroll
     for (int t4 = 0; t4 < NQ; ++t4) o[ds][t4] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float lrow[NQ];
-#pragma unroll
-  for (int t4 = 0; t4 < NQ; ++t4) lrow[t4] = 0.f;
-  // RS: row sums as one more MFMA per query tile and key half (ones^T P: every accumulator row
-  // holds the query's partial sum) instead of 16 VALU adds per query tile and key half
-  f32x4 lacc[NQ];
+  f32x4 lacc[NQ];  // row sums: ones^T P
 #pragma unroll
   for (int t4 = 0; t4 < NQ; ++t4) lacc[t4] = f32x4{0.f, 0.f, 0.f, 0.f};
   bf16x8 ones;
@@ -692,26 +663,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_k(FwdP p) {
         bf16x8 pf[NQ];
 #pragma unroll
         for (int t4 = 0; t4 < NQ; ++t4) {
-          if (RS) {
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
+          for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-              for (int r = 0; r < 4; ++r) st[kk][t4][r] = __builtin_amdgcn_exp2f(st[kk][t4][r]);
-          } else {
-            float ps0 = 0.f, ps1 = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < 2; ++kk)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float pv = __builtin_amdgcn_exp2f(st[kk][t4][r]);
-                st[kk][t4][r] = pv;
-                if (r & 1)
-                  ps1 += pv;
-                else
-                  ps0 += pv;
-              }
-            lrow[t4] += ps0 + ps1;
-          }
+            for (int r = 0; r < 4; ++r) st[kk][t4][r] = __builtin_amdgcn_exp2f(st[kk][t4][r]);
           pf[t4] = pack_perm(st[0][t4], st[1][t4]);
         }
 #pragma unroll
@@ -721,11 +676,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_k(FwdP p) {
           for (int t4 = 0; t4 < NQ; ++t4)
             o[ds][t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vt, pf[t4], o[ds][t4], 0, 0, 0);
         }
-        if (RS) {
 #pragma unroll
-          for (int t4 = 0; t4 < NQ; ++t4)
-            lacc[t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[t4], lacc[t4], 0, 0, 0);
-        }
+        for (int t4 = 0; t4 < NQ; ++t4)
+          lacc[t4] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[t4], lacc[t4], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);  // one key half's S / P live at a time (register budget)
       }
     }
@@ -736,17 +689,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_k(FwdP p) {
   // D = 64: O goes through this wave's 8 KiB of the (drained) ring and is stored as whole 128-B rows
   // with 16-B stores, 8 per lane instead of 16 lane-held 8-B pieces (the store tail ends the
   // workgroup).  Row r = query r0 + r, 16-B chunk x at x ^ (r & 7)
-  constexpr bool STAGE = D == 64 && OWLK_FWD_STAGE && NQ * 16 * 128 * 4 <= NBUF * TILEB;
+  constexpr bool STAGE = D == 64 && NQ * 16 * 128 * 4 <= NBUF * TILEB;
   char* stg = smem + w * (NQ * 16 * 128);
 #pragma unroll
   for (int t4 = 0; t4 < NQ; ++t4) {
-    float ltot;
-    if (RS) {
-      ltot = lacc[t4][0];  // every row of ones^T P holds the full sum over the keys
-    } else {
-      ltot = lrow[t4] + __shfl_xor(lrow[t4], 16, 64);
-      ltot += __shfl_xor(ltot, 32, 64);
-    }
+    const float ltot = lacc[t4][0];  // every row of ones^T P holds the full sum over the keys
     const float inv = ltot > 0.f ? 1.f / ltot : 0.f;
     if constexpr (STAGE) {
       const int r = 16 * t4 + c;
@@ -1184,92 +1131,75 @@ __global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointP p) {
   }
 }
 
+// Sweeps of at least this many keys (unwindowed masks, or windows this long) take the forms with
+// larger per-workgroup tiles; short windowed sweeps are dominated by their prologue and mask-edge tiles
+static bool long_sweep(const MaskP& m) { return m.window <= 0 || (long)m.window * m.tpf >= 4096; }
+
 template <int D>
 void launch_fwd(const FwdP& p, dim3 grid, hipStream_t s) {
-  static const int two = getenv("OWLK_FWD2") ? atoi(getenv("OWLK_FWD2")) : 1;
-  static const int f16 = getenv("OWLK_FWD16") ? atoi(getenv("OWLK_FWD16")) : 1;  // 16x16x32 variant (0: off)
-  static const int rs = getenv("OWLK_FWD_RS") ? atoi(getenv("OWLK_FWD_RS")) : 1;  // row sums on the MFMA (0: VALU adds)
-  // decode: one unmasked <= 64-query block per (batch, head) over >= 4 key tiles
-  static const int split = getenv("OWLK_FWD_SPLIT") ? atoi(getenv("OWLK_FWD_SPLIT")) : 1;
   const MaskP& m = p.m;
+  // decode: one unmasked <= 64-query block per (batch, head) over >= 4 key tiles (OWLK_FWD_SPLIT = 0:
+  // the training kernels, for tools/attn_decode_bench.py's A/B)
+  static const int split = getenv("OWLK_FWD_SPLIT") ? atoi(getenv("OWLK_FWD_SPLIT")) : 1;
   if (split && p.bound > 0.f && p.Lq <= 64 && p.Lkv >= 4 * KT && m.window == 0 && !m.causal && !m.kv_lo &&
       !m.doc && m.q_offset == 0) {
     hipLaunchKernelGGL(attn_fwd16_split_k<D>, dim3(1, grid.y, grid.z), dim3(256), 0, s, p, (const long*)nullptr,
                        0L, 0L, 0L);
     return;
   }
-  // D 64, bounded softmax, frame mask without documents: the one-wave-per-SIMD forward (attn_fwd4.hip;
-  // OWLK_FWD4=0 keeps attn_fwd16_k, read per call so tests can compare the two)
-  if constexpr (D == 64) {
-    const char* e4 = getenv("OWLK_FWD4");
-    // long sweeps only (global or >= 4096-token windows): at window 16 (1,024 keys) the 512-query
-    // workgroups leave the chip a quarter as many blocks and the run's prologue / drain dominate
-    // (0.73 -> 1.13 ms, profiles/r6z)
-    const bool long4 = p.m.window <= 0 || (long)p.m.window * p.m.tpf >= 4096;
-    if ((!e4 || atoi(e4) != 0) && f16 && p.bound > 0.f && rs && long4) {
-      Fwd4P p4;
-      p4.q = p.q;
-      p4.k = p.k;
-      p4.v = p.v;
-      p4.o = p.o;
-      p4.lse = p.lse;
-      p4.ldq = p.ldq;
-      p4.ldk = p.ldk;
-      p4.ldv = p.ldv;
-      p4.ldo = p.ldo;
-      p4.sqb = p.sqb;
-      p4.skb = p.skb;
-      p4.svb = p.svb;
-      p4.sob = p.sob;
-      p4.Lq = p.Lq;
-      p4.Lkv = p.Lkv;
-      p4.H = p.H;
-      p4.B = (int)grid.z;
-      p4.scale_log2 = p.scale_log2;
-      p4.m = p.m;
-      if (owlk_fwd4_launch(p4, s) == 0) return;
-    }
-  }
-  // D 128: the 16x16x32 form with 32 queries per wave (OWLK_FWD16_128=0: the 32x32x16 attn_fwd_k)
-  static const int f16_128 = getenv("OWLK_FWD16_128") ? atoi(getenv("OWLK_FWD16_128")) : 1;
-  if (f16 && p.bound > 0.f && (D == 64 || f16_128)) {
-    const dim3 g2((unsigned)((p.Lq + F16Cfg<D>::QTW - 1) / F16Cfg<D>::QTW), grid.y, grid.z);
-    // long sweeps (unwindowed, or windows of >= 4096 tokens): D 64 takes 128-key tiles (global 24.46
-    // -> 24.00 ms at the dit_v4 shape; OWLK_FWD_KT128 = 0 turns it off), D 128 48 queries per wave
-    // (global 46.5 -> 41.5 ms at the dit_v4_5B shape; OWLK_FWD_NQ3 = 0); window 16 keeps the base form
-    const bool long_sweep = m.window <= 0 || (long)m.window * m.tpf >= 4096;
-    static const int kt128 = getenv("OWLK_FWD_KT128") ? atoi(getenv("OWLK_FWD_KT128")) : 1;
-    static const int nq3 = getenv("OWLK_FWD_NQ3") ? atoi(getenv("OWLK_FWD_NQ3")) : 1;
+  if (p.bound > 0.f) {
+    // D 64, long sweeps, frame mask without documents: the one-wave-per-SIMD forward (attn_fwd4.hip;
+    // OWLK_FWD4 = 0 keeps attn_fwd16_k, read per call so tests can compare the two).  Not at window
+    // 16 (1,024 keys): the 512-query workgroups leave the chip a quarter as many blocks and the run's
+    // prologue / drain dominate (0.73 -> 1.13 ms, profiles/r6z)
     if constexpr (D == 64) {
-      if (rs && kt128 && long_sweep) {
-        hipLaunchKernelGGL((attn_fwd16_k<D, true, 128>), g2, dim3(256), 0, s, p);
-        return;
-      }
-    } else {
-      if (rs && nq3 && long_sweep) {
-        const dim3 g3((unsigned)((p.Lq + 191) / 192), grid.y, grid.z);
-        hipLaunchKernelGGL((attn_fwd16_k<D, true, KT, 3>), g3, dim3(256), 0, s, p);
-        return;
+      const char* e4 = getenv("OWLK_FWD4");
+      if ((!e4 || atoi(e4) != 0) && long_sweep(m)) {
+        Fwd4P p4;
+        p4.q = p.q;
+        p4.k = p.k;
+        p4.v = p.v;
+        p4.o = p.o;
+        p4.lse = p.lse;
+        p4.ldq = p.ldq;
+        p4.ldk = p.ldk;
+        p4.ldv = p.ldv;
+        p4.ldo = p.ldo;
+        p4.sqb = p.sqb;
+        p4.skb = p.skb;
+        p4.svb = p.svb;
+        p4.sob = p.sob;
+        p4.Lq = p.Lq;
+        p4.Lkv = p.Lkv;
+        p4.H = p.H;
+        p4.B = (int)grid.z;
+        p4.scale_log2 = p.scale_log2;
+        p4.m = p.m;
+        if (owlk_fwd4_launch(p4, s) == 0) return;
       }
     }
-    if (rs)
-      hipLaunchKernelGGL((attn_fwd16_k<D, true>), g2, dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL((attn_fwd16_k<D, false>), g2, dim3(256), 0, s, p);
+    // attn_fwd16_k.  Long sweeps: D 64 takes 128-key tiles (global 24.46 -> 24.00 ms at the dit_v4
+    // shape), D 128 48 queries per wave (global 46.5 -> 41.5 ms at the dit_v4_5B shape); short
+    // windows (window 16) keep the base form
+    if (D == 64 && long_sweep(m)) {
+      const dim3 g((unsigned)((p.Lq + F16Cfg<64>::QTW - 1) / F16Cfg<64>::QTW), grid.y, grid.z);
+      hipLaunchKernelGGL((attn_fwd16_k<64, 128>), g, dim3(256), 0, s, p);
+    } else if (D == 128 && long_sweep(m)) {
+      const dim3 g((unsigned)((p.Lq + 191) / 192), grid.y, grid.z);
+      hipLaunchKernelGGL((attn_fwd16_k<128, KT, 3>), g, dim3(256), 0, s, p);
+    } else {
+      const dim3 g((unsigned)((p.Lq + F16Cfg<D>::QTW - 1) / F16Cfg<D>::QTW), grid.y, grid.z);
+      hipLaunchKernelGGL((attn_fwd16_k<D>), g, dim3(256), 0, s, p);
+    }
     return;
   }
-  if (D == 64 && two) {
+  // score_bound = 0: the running-max kernels
+  if constexpr (D == 64) {
     const dim3 g2((unsigned)((p.Lq + QT2 - 1) / QT2), grid.y, grid.z);
-    if (p.bound > 0.f)
-      hipLaunchKernelGGL((attn_fwd2_k<true>), g2, dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL((attn_fwd2_k<false>), g2, dim3(256), 0, s, p);
-    return;
+    hipLaunchKernelGGL(attn_fwd2_k, g2, dim3(256), 0, s, p);
+  } else {
+    hipLaunchKernelGGL(attn_fwd_k<D>, grid, dim3(256), 0, s, p);
   }
-  if (p.bound > 0.f)
-    hipLaunchKernelGGL((attn_fwd_k<D, true>), grid, dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((attn_fwd_k<D, false>), grid, dim3(256), 0, s, p);
 }
 
 }  // namespace
