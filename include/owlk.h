@@ -157,6 +157,26 @@ int owlk_qk_rope_fwd_kv_dev(const void* qkv, long ldq, long T, long L, int H, in
                             const float* sinb, long ld_tab, long n_tab, const long* state, void* qo, long ldqo,
                             long sqo, void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
                             void* stream);
+/* Ring form of owlk_qk_rope_fwd_kv_dev for endless frame streaming (the reference's
+ * inference/causvid_pipeline.py: pipe(new_mouse, new_btn) -> frame; attn.py:83-104 cache branch): the
+ * same arguments and arithmetic, but kbuf / vbuf are rings of cap rows and token t's k / v go to row
+ * (start + cached + t) mod cap.  Contract: 0 <= start < cap, cached + L <= cap, table rows inside n_tab;
+ * outside it NaN q rows, cache and table untouched. */
+int owlk_qk_rope_fwd_kv_ring(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
+                             const float* sinb, long ld_tab, long n_tab, const long* state, void* qo, long ldqo,
+                             long sqo, void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
+                             void* stream);
+/* RoPE rebase between streamed frames (causvid_pipeline.py generates past the rope.py:40-49 table;
+ * MotionRoPE / Audio1DRoPE angles, rope.py:82-179, are linear in the frame index, so q.k depends only
+ * on frame differences).  In place over the `rows` live logical rows of the ring K buffer kbuf
+ * [B, cap, H D] (logical row i at physical row (start + i) mod cap): the row stored rotated by table row
+ * old_off + i becomes the rotation of table row new_off + i.  fp32 from the two table rows,
+ * cos D = c_n c_o + s_n s_o, sin D = s_n c_o - c_n s_o, on the stored pairs (p, D/2 + p), one bf16
+ * rounding.  Host positions (between frames, outside a captured graph); both row ranges must lie in
+ * the n_tab table rows and 0 <= start < cap, rows <= cap (else returns 1).  V needs no rebase. */
+int owlk_rope_rebase(void* kbuf, long ldk, long skb, long B, int H, int D, long start, long rows, long cap,
+                     const float* cosb, const float* sinb, long ld_tab, long n_tab, long old_off, long new_off,
+                     void* stream);
 /* MMDiT decode form (mmattn.py:46-86): the joint frames [n0 video | n1 audio] read straight from the
  * two modalities' qkv GEMM outputs (joint row r of frame f of batch b: video row (b nf + f) n0 + r for
  * r < n0, else audio row (b nf + f) n1 + r - n0), table row tab_off + f (n0 + n1) + r.  q goes to a
@@ -209,6 +229,16 @@ int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const void* kbuf, lo
                          const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse, long B,
                          int H, long Lq, int head_dim, float scale, float score_bound, const long* state,
                          long Lnew, long window_tokens, long cap, void* stream);
+/* Ring form of owlk_attn_decode_fwd for endless frame streaming (the reference's
+ * inference/causvid_pipeline.py on the attn.py:86-107 cache branch): the same arguments, but logical key
+ * i of [cache | Lnew new rows] lives at physical row (start + i) mod cap of kbuf / vbuf; window_tokens
+ * applies to logical keys.  Same tile decomposition as the linear kernel (each DMA row's address wraps),
+ * so o and lse equal owlk_attn_decode_fwd's on an unrolled copy of the buffers bit for bit.  Contract:
+ * 0 <= start < cap, cached + Lnew <= cap; outside it NaN output, nothing read. */
+int owlk_attn_decode_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                              const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse, long B,
+                              int H, long Lq, int head_dim, float scale, float score_bound, const long* state,
+                              long Lnew, long window_tokens, long cap, void* stream);
 /* Joint-frame decode attention (mmattn.py:46-86, one new MMDiT frame against the cache): per (batch,
  * head) the n0 + n1 <= 80 query rows of q [B, n0 + n1, H D] (row stride ldq, batch stride sqb),
  * unmasked over Lkv key rows k / v (pointer + strides: [cache | new], or its last window rows for a

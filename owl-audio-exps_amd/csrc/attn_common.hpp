@@ -316,6 +316,25 @@ DEV void tile_glds(char* lds, const bf16* base, long ld, long r0, long R, int wa
   }
 }
 
+// tile_glds over a ring of `cap` rows: logical row r (clamped to R - 1 as above) lives at physical
+// row org + r, minus cap once past the end (0 <= org < cap, R <= cap: one compare per lane row).
+// The wrap is per row, so a tile or a 16-row DMA group may straddle the end of the buffer.
+template <int S>
+DEV void tile_glds_ring(char* lds, const bf16* base, long ld, long r0, long R, long org, long cap, int wave,
+                        int lane) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int row = 16 * wave + 8 * i + (lane >> 3);
+    const int ch = (lane & 7) ^ swz<S>(row);
+    long gr = r0 + row;
+    gr = (gr < R ? gr : R - 1) + org;
+    gr = gr < cap ? gr : gr - cap;
+    __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*)(base + gr * ld + ch * 8),
+                                     (void __attribute__((address_space(3)))*)(lds + (16 * wave + 8 * i) * 128), 16,
+                                     0, 0);
+  }
+}
+
 // Same transfer with per-lane byte offsets precomputed once (they do not depend on the tile) and
 // a wave-uniform tile base, so each tile costs no VALU address arithmetic (saddr + voffset form).
 // Only for tiles fully inside the tensor (the caller keeps tile_glds for the ragged last tile).

@@ -754,7 +754,11 @@ struct DecCfg {
   static constexpr int OPS = 2 * (KTD / 16) * 2 * NSUB;  // LDS-DMA wave-instructions per tile
 };
 
-template <int D>
+// RING (owlk_attn_decode_ring_fwd): the buffers are rings of cap rows -- logical key i of [cache | new]
+// lives at physical row (start + i) mod cap.  The tile decomposition stays the logical one (tile
+// w + 4 i of wave w from the first visible key), only each DMA row's source address wraps, so the
+// result equals the linear kernel's on an unrolled copy of the buffers bit for bit.
+template <int D, bool RING = false>
 __global__ __launch_bounds__(256, 1) void attn_fwd16_split_k(FwdP p, const long* __restrict__ state, long Lnew,
                                                              long wtok, long cap) {
   // device-resident cache state (owlk_attn_decode_fwd): {start, cached tokens, rope offset} of the
@@ -762,7 +766,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd16_split_k(FwdP p, const long*
   // keys are [cache | the Lnew new rows], the last wtok of them for a windowed layer (wtok > 0)
   if (state) {
     const long start = state[0], total = state[1] + Lnew;
-    if (start < 0 || state[1] < 0 || start + total > cap) {
+    if (start < 0 || state[1] < 0 || (RING ? start >= cap || total > cap : start + total > cap)) {
       // a window past the cap rows of the buffers: read nothing, NaN rows out (the host checks
       // every position it sets; this guards a replayed graph)
       const long b = blockIdx.z;
@@ -780,9 +784,20 @@ __global__ __launch_bounds__(256, 1) void attn_fwd16_split_k(FwdP p, const long*
       return;
     }
     const long first = wtok > 0 && total > wtok ? total - wtok : 0;
-    p.k += (start + first) * p.ldk;
-    p.v += (start + first) * p.ldv;
+    if constexpr (!RING) {
+      p.k += (start + first) * p.ldk;
+      p.v += (start + first) * p.ldv;
+    }
     p.Lkv = total - first;
+  }
+  // RING: physical row of the first visible key (the ring entry always has a state; formed apart from
+  // the block above so that the linear instantiation's code stays what it was, instruction for
+  // instruction)
+  long org = 0;
+  if constexpr (RING) {
+    const long total = state[1] + Lnew;
+    org = state[0] + (wtok > 0 && total > wtok ? total - wtok : 0);
+    org = org < cap ? org : org - cap;
   }
   using C = DecCfg<D>;
   constexpr int KTD = C::KTD;
@@ -827,8 +842,14 @@ __global__ __launch_bounds__(256, 1) void attn_fwd16_split_k(FwdP p, const long*
     for (int sb = 0; sb < C::NSUB; ++sb)
 #pragma unroll
       for (int q4 = 0; q4 < KTD / 16; ++q4) {
-        tile_glds<SW_ROW>(buf + sb * C::SUBK, K + 64 * sb, p.ldk, c0, p.Lkv, q4, lane);
-        tile_glds<SW_DUAL>(buf + (C::NSUB + sb) * C::SUBK, V + 64 * sb, p.ldv, c0, p.Lkv, q4, lane);
+        if constexpr (RING) {
+          tile_glds_ring<SW_ROW>(buf + sb * C::SUBK, K + 64 * sb, p.ldk, c0, p.Lkv, org, cap, q4, lane);
+          tile_glds_ring<SW_DUAL>(buf + (C::NSUB + sb) * C::SUBK, V + 64 * sb, p.ldv, c0, p.Lkv, org, cap, q4,
+                                  lane);
+        } else {
+          tile_glds<SW_ROW>(buf + sb * C::SUBK, K + 64 * sb, p.ldk, c0, p.Lkv, q4, lane);
+          tile_glds<SW_DUAL>(buf + (C::NSUB + sb) * C::SUBK, V + 64 * sb, p.ldv, c0, p.Lkv, q4, lane);
+        }
       }
   };
   if (nt > 0) issue(0);
@@ -1250,10 +1271,10 @@ extern "C" int owlk_attn_fwd(const void* q, long ldq, long sqb, const void* k, l
   return owlk::check_launch("attn_fwd");
 }
 
-extern "C" int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
-                                    const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
-                                    long B, int H, long Lq, int head_dim, float scale, float score_bound,
-                                    const long* state, long Lnew, long window_tokens, long cap, void* stream) {
+static int attn_decode_launch(bool ring, const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                              const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse, long B,
+                              int H, long Lq, int head_dim, float scale, float score_bound, const long* state,
+                              long Lnew, long window_tokens, long cap, void* stream) {
   OWLK_REQUIRE(head_dim == 64 || head_dim == 128, "attn_decode_fwd: head_dim %d not built (64, 128)", head_dim);
   OWLK_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lq <= 64 && Lnew > 0 && state, "attn_decode_fwd: bad sizes");
   OWLK_REQUIRE(cap >= Lnew, "attn_decode_fwd: cache capacity %ld rows", cap);
@@ -1269,13 +1290,41 @@ extern "C" int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const voi
   p.scale_log2 = scale * LOG2E;
   p.bound = score_bound;
   p.m = owlk_make_mask(1, 0, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, 0);
-  if (head_dim == 64)
-    hipLaunchKernelGGL(attn_fwd16_split_k<64>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       p, state, Lnew, window_tokens, cap);
+  const dim3 grid(1, (unsigned)H, (unsigned)B);
+  if (ring && head_dim == 64)
+    hipLaunchKernelGGL((attn_fwd16_split_k<64, true>), grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
+                       window_tokens, cap);
+  else if (ring)
+    hipLaunchKernelGGL((attn_fwd16_split_k<128, true>), grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
+                       window_tokens, cap);
+  else if (head_dim == 64)
+    hipLaunchKernelGGL(attn_fwd16_split_k<64>, grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
+                       window_tokens, cap);
   else
-    hipLaunchKernelGGL(attn_fwd16_split_k<128>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                       p, state, Lnew, window_tokens, cap);
-  return owlk::check_launch("attn_decode_fwd");
+    hipLaunchKernelGGL(attn_fwd16_split_k<128>, grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
+                       window_tokens, cap);
+  return owlk::check_launch(ring ? "attn_decode_ring_fwd" : "attn_decode_fwd");
+}
+
+extern "C" int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                    const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
+                                    long B, int H, long Lq, int head_dim, float scale, float score_bound,
+                                    const long* state, long Lnew, long window_tokens, long cap, void* stream) {
+  return attn_decode_launch(false, q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o, ldo, sob, lse, B, H, Lq, head_dim,
+                            scale, score_bound, state, Lnew, window_tokens, cap, stream);
+}
+
+// Ring form for endless frame streaming (the reference's inference/causvid_pipeline.py: pipe(new_mouse,
+// new_btn) -> frame, on the attn.py:86-107 cache branch): logical key i of [cache | Lnew new rows] lives
+// at physical row (start + i) mod cap of kbuf / vbuf, so the cache never moves or grows.  Contract:
+// 0 <= start < cap, cached + Lnew <= cap; outside it NaN output and nothing read.
+extern "C" int owlk_attn_decode_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                         const void* vbuf, long ldv, long svb, void* o, long ldo, long sob,
+                                         float* lse, long B, int H, long Lq, int head_dim, float scale,
+                                         float score_bound, const long* state, long Lnew, long window_tokens,
+                                         long cap, void* stream) {
+  return attn_decode_launch(true, q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o, ldo, sob, lse, B, H, Lq, head_dim,
+                            scale, score_bound, state, Lnew, window_tokens, cap, stream);
 }
 
 extern "C" int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, const void* k, long ldk, long skb,

@@ -400,7 +400,9 @@ __global__ __launch_bounds__(256) void qk_rope_fwd_k(const bf16* __restrict__ qk
 // decode form: the same q / k rotation with q, k and a copy of v written to three destinations with
 // their own row and batch strides (token t of batch t / L, row t % L) -- k and v straight into the
 // KV cache's slots behind the cached window, so the decode step needs no separate cache copies
-template <int D>
+// RING (owlk_qk_rope_fwd_kv_ring): the buffers are rings of cap rows, token t's k / v go to row
+// (start + cached + t) mod cap
+template <int D, bool RING = false>
 __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv, long ldq, long T, long L, int H,
                                                     const float* __restrict__ cosb, const float* __restrict__ sinb,
                                                     long ld_tab, long tab_off, bf16* __restrict__ qo, long ldqo,
@@ -417,7 +419,8 @@ __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv
   const long bb = tok / L, t = tok - bb * L;
   if (state) {  // {start, cached tokens, rope offset}: k / v rows go behind the window of the buffers
     const long start = state[0], cached = state[1], off = state[2];
-    if (start < 0 || cached < 0 || start + cached + L > cap || off < 0 || off + L > n_tab) {
+    if (start < 0 || cached < 0 || (RING ? start >= cap || cached + L > cap : start + cached + L > cap) || off < 0 ||
+        off + L > n_tab) {
       // a position past the cache buffers or the rope table (the host checks every position it
       // sets; this guards the replayed graph): touch neither, poison this row of q with NaN
       if (wh < H) {
@@ -428,8 +431,14 @@ __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv
       }
       return;
     }
-    ko += (start + cached) * ldko;
-    vo += (start + cached) * ldvo;
+    if constexpr (RING) {  // this token's row wraps on its own (the new rows may straddle the end)
+      const long r = start + cached + t, pr = r < cap ? r : r - cap;
+      ko += (pr - t) * ldko;
+      vo += (pr - t) * ldvo;
+    } else {
+      ko += (start + cached) * ldko;
+      vo += (start + cached) * ldvo;
+    }
     tab_off = off;
   }
   const bf16x8 v = *(const bf16x8*)(qkv + tok * ldq + (long)wh * D + j * 8);
@@ -456,6 +465,43 @@ __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv
     y1[i] = (bf16)(x1 * c[i] + x0 * s[i]);
   }
   bf16* o = wh < H ? qo + bb * sqo + t * ldqo + (long)wh * D : ko + bb * sko + t * ldko + (long)(wh - H) * D;
+  *(bf16x4*)(o + j * 4) = y0;
+  *(bf16x4*)(o + D / 2 + j * 4) = y1;
+}
+
+// RoPE rebase (owlk_rope_rebase): live logical row i of a ring K buffer, stored rotated by table row
+// old_off + i, is re-rotated in place to table row new_off + i.  The angle difference comes from the
+// two table rows in fp32 (cos D = c_n c_o + s_n s_o, sin D = s_n c_o - c_n s_o), applied to the
+// stored (first half | second half) pairs (p, D/2 + p) with one final bf16 rounding.  Each thread owns
+// the 4 pairs it reads and writes, so in place needs no ordering.
+template <int D>
+__global__ __launch_bounds__(256) void rope_rebase_k(bf16* __restrict__ kbuf, long ldk, long skb, long B, int H,
+                                                     long start, long rows, long cap,
+                                                     const float* __restrict__ cosb, const float* __restrict__ sinb,
+                                                     long ld_tab, long old_off, long new_off) {
+  constexpr int CPR = D / 8;
+  const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+  const long rowid = gid / CPR;  // (batch, row, head)
+  const int j = gid % CPR;
+  if (rowid >= B * rows * H) return;
+  const int head = rowid % H;
+  const long i = (rowid / H) % rows, bb = rowid / (H * rows);
+  long pr = start + i;
+  pr = pr < cap ? pr : pr - cap;
+  bf16* o = kbuf + bb * skb + pr * ldk + (long)head * D;
+  const f32x4 co = *(const f32x4*)(cosb + (old_off + i) * ld_tab + j * 4);
+  const f32x4 so = *(const f32x4*)(sinb + (old_off + i) * ld_tab + j * 4);
+  const f32x4 cn = *(const f32x4*)(cosb + (new_off + i) * ld_tab + j * 4);
+  const f32x4 sn = *(const f32x4*)(sinb + (new_off + i) * ld_tab + j * 4);
+  const bf16x4 a = *(const bf16x4*)(o + j * 4), b = *(const bf16x4*)(o + D / 2 + j * 4);
+  bf16x4 y0, y1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float cd = cn[e] * co[e] + sn[e] * so[e], sd = sn[e] * co[e] - cn[e] * so[e];
+    const float x0 = (float)a[e], x1 = (float)b[e];
+    y0[e] = (bf16)(x0 * cd - x1 * sd);
+    y1[e] = (bf16)(x1 * cd + x0 * sd);
+  }
   *(bf16x4*)(o + j * 4) = y0;
   *(bf16x4*)(o + D / 2 + j * 4) = y1;
 }
@@ -941,7 +987,7 @@ extern "C" int owlk_qk_rope_fwd(const void* qkv, long ldq, long T, int H, int D,
 static int qk_rope_kv_launch(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
                              const float* sinb, long ld_tab, long n_tab, long tab_off, void* qo, long ldqo, long sqo,
                              void* ko, long ldko, long sko, void* vo, long ldvo, long svo, const long* state,
-                             long cap, void* stream);
+                             long cap, bool ring, void* stream);
 
 
 extern "C" int owlk_qk_rope_fwd_kv(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
@@ -951,7 +997,7 @@ extern "C" int owlk_qk_rope_fwd_kv(const void* qkv, long ldq, long T, long L, in
   OWLK_REQUIRE(L > 0 && rope_rows_ok(L, n_tab, tab_off, 0), "qk_rope_fwd_kv: positions %ld.. past the %ld-row rope table",
                tab_off, n_tab);
   return qk_rope_kv_launch(qkv, ldq, T, L, H, D, cosb, sinb, ld_tab, n_tab, tab_off, qo, ldqo, sqo, ko, ldko, sko, vo,
-                           ldvo, svo, nullptr, 0, stream);
+                           ldvo, svo, nullptr, 0, false, stream);
 }
 
 extern "C" int owlk_qk_rope_fwd_kv_dev(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
@@ -961,13 +1007,57 @@ extern "C" int owlk_qk_rope_fwd_kv_dev(const void* qkv, long ldq, long T, long L
   OWLK_REQUIRE(state, "qk_rope_fwd_kv_dev: state pointer required");
   OWLK_REQUIRE(n_tab > 0 && cap > 0, "qk_rope_fwd_kv_dev: rope table rows / cache capacity required");
   return qk_rope_kv_launch(qkv, ldq, T, L, H, D, cosb, sinb, ld_tab, n_tab, 0, qo, ldqo, sqo, kbuf, ldk, skb, vbuf, ldv,
-                           svb, state, cap, stream);
+                           svb, state, cap, false, stream);
+}
+
+// Ring form for endless frame streaming (the reference's inference/causvid_pipeline.py: pipe(new_mouse,
+// new_btn) -> frame, on the attn.py:83-104 cache branch): owlk_qk_rope_fwd_kv_dev with token t's k / v
+// at row (start + cached + t) mod cap.  Contract: 0 <= start < cap, cached + L <= cap, table rows inside
+// n_tab; outside it NaN q rows, cache and table untouched.
+extern "C" int owlk_qk_rope_fwd_kv_ring(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
+                                        const float* sinb, long ld_tab, long n_tab, const long* state, void* qo,
+                                        long ldqo, long sqo, void* kbuf, long ldk, long skb, void* vbuf, long ldv,
+                                        long svb, long cap, void* stream) {
+  OWLK_REQUIRE(state, "qk_rope_fwd_kv_ring: state pointer required");
+  OWLK_REQUIRE(n_tab > 0 && cap > 0, "qk_rope_fwd_kv_ring: rope table rows / cache capacity required");
+  return qk_rope_kv_launch(qkv, ldq, T, L, H, D, cosb, sinb, ld_tab, n_tab, 0, qo, ldqo, sqo, kbuf, ldk, skb, vbuf, ldv,
+                           svb, state, cap, true, stream);
+}
+
+// RoPE rebase between streamed frames (causvid_pipeline.py keeps generating past the rope.py:40-49 table;
+// MotionRoPE / Audio1DRoPE angles, rope.py:82-179, are linear in the frame index, so q.k depends only on
+// frame differences): the `rows` live logical rows of the ring K buffer kbuf [B, cap, H D], from
+// physical row start, go from the rotation of table rows old_off.. to that of new_off.. in place.
+// Host positions (it runs between frames, outside a captured graph); V is not touched.
+extern "C" int owlk_rope_rebase(void* kbuf, long ldk, long skb, long B, int H, int D, long start, long rows,
+                                long cap, const float* cosb, const float* sinb, long ld_tab, long n_tab,
+                                long old_off, long new_off, void* stream) {
+  OWLK_REQUIRE(D == 64 || D == 128, "rope_rebase: head_dim %d unsupported", D);
+  OWLK_REQUIRE(B > 0 && H > 0 && cap > 0 && start >= 0 && start < cap && rows >= 0 && rows <= cap,
+               "rope_rebase: bad ring window start=%ld rows=%ld cap=%ld", start, rows, cap);
+  OWLK_REQUIRE(n_tab > 0 && old_off >= 0 && old_off + rows <= n_tab,
+               "rope_rebase: old positions %ld..%ld past the %ld-row rope table", old_off, old_off + rows - 1, n_tab);
+  OWLK_REQUIRE(new_off >= 0 && new_off + rows <= n_tab,
+               "rope_rebase: new positions %ld..%ld past the %ld-row rope table", new_off, new_off + rows - 1, n_tab);
+  OWLK_REQUIRE((uintptr_t)kbuf % 16 == 0 && ldk % 8 == 0 && skb % 8 == 0 && ldk >= (long)H * D && ld_tab % 4 == 0 &&
+                   ((uintptr_t)cosb | (uintptr_t)sinb) % 16 == 0,
+               "rope_rebase: buffer rows and table rows must be 16-byte aligned");
+  if (rows == 0 || old_off == new_off) return 0;
+  const long threads = B * rows * H * (D / 8);
+  dim3 g((unsigned)((threads + 255) / 256));
+  if (D == 64)
+    hipLaunchKernelGGL(rope_rebase_k<64>, g, dim3(256), 0, (hipStream_t)stream, (bf16*)kbuf, ldk, skb, B, H, start,
+                       rows, cap, cosb, sinb, ld_tab, old_off, new_off);
+  else
+    hipLaunchKernelGGL(rope_rebase_k<128>, g, dim3(256), 0, (hipStream_t)stream, (bf16*)kbuf, ldk, skb, B, H, start,
+                       rows, cap, cosb, sinb, ld_tab, old_off, new_off);
+  return owlk::check_launch("rope_rebase");
 }
 
 static int qk_rope_kv_launch(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
                              const float* sinb, long ld_tab, long n_tab, long tab_off, void* qo, long ldqo, long sqo,
                              void* ko, long ldko, long sko, void* vo, long ldvo, long svo, const long* state,
-                             long cap, void* stream) {
+                             long cap, bool ring, void* stream) {
   OWLK_REQUIRE(D == 64 || D == 128, "qk_rope_fwd_kv: head_dim %d unsupported", D);
   OWLK_REQUIRE(L > 0 && T % L == 0, "qk_rope_fwd_kv: T=%ld is not a whole number of L=%ld rows", T, L);
   OWLK_REQUIRE(((uintptr_t)qo | (uintptr_t)ko | (uintptr_t)vo) % 16 == 0 && ldqo % 8 == 0 && ldko % 8 == 0 &&
@@ -975,7 +1065,15 @@ static int qk_rope_kv_launch(const void* qkv, long ldq, long T, long L, int H, i
                "qk_rope_fwd_kv: destinations must be 16-byte aligned");
   const long threads = T * 3 * H * (D / 8);
   dim3 g((unsigned)((threads + 255) / 256));
-  if (D == 64)
+  if (ring && D == 64)
+    hipLaunchKernelGGL((qk_rope_kv_k<64, true>), g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, ldq, T, L, H,
+                       cosb, sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo, (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo,
+                       state, n_tab, cap);
+  else if (ring)
+    hipLaunchKernelGGL((qk_rope_kv_k<128, true>), g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, ldq, T, L, H,
+                       cosb, sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo, (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo,
+                       state, n_tab, cap);
+  else if (D == 64)
     hipLaunchKernelGGL(qk_rope_kv_k<64>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, ldq, T, L, H, cosb,
                        sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo, (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo, state,
                        n_tab, cap);

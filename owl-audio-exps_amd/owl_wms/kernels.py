@@ -354,6 +354,45 @@ def attn_decode_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0, scale=Non
     return o, lse
 
 
+def qk_rope_fwd_kv_ring(qkv, B, L, H, D, cos, sin, state, q_out, kbuf, vbuf):
+    """qk_rope_fwd_kv_dev on ring buffers: k / v of token t go to row (start + cached + t) mod cap of
+    kbuf / vbuf [B, cap, H D] (RingKVCache); 0 <= start < cap and cached + L <= cap."""
+    assert state.dtype == torch.int64 and state.numel() >= 3 and state.is_cuda
+    assert q_out.shape == (B, L, H * D) and q_out.stride(2) == 1
+    for t in (kbuf, vbuf):
+        assert t.dim() == 3 and t.shape[0] == B and t.shape[2] == H * D and t.stride(2) == 1 and t.dtype == BF16
+    assert kbuf.shape[1] == vbuf.shape[1]
+    call("owlk_qk_rope_fwd_kv_ring", ptr(qkv), qkv.stride(0), B * L, L, H, D, ptr(cos), ptr(sin), cos.stride(0),
+         cos.shape[0], ptr(state), ptr(q_out), q_out.stride(1), q_out.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), kbuf.shape[1], stream())
+
+
+def attn_decode_ring_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0, scale=None, score_bound=0.0):
+    """attn_decode_fwd on ring buffers: logical key i of [cache | Lnew new rows] at physical row
+    (start + i) mod cap; the same bits as attn_decode_fwd on an unrolled copy of the buffers."""
+    B, Lq, _ = q.shape
+    assert decode_dev_supported(D, Lq), f"attn_decode_ring_fwd: head_dim {D} / {Lq} query rows not supported"
+    assert kbuf.shape[1] == vbuf.shape[1], "ring buffers of one capacity"
+    o = torch.empty_like(q)
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32)
+    call("owlk_attn_decode_ring_fwd", ptr(q), q.stride(1), q.stride(0), ptr(kbuf), kbuf.stride(1), kbuf.stride(0),
+         ptr(vbuf), vbuf.stride(1), vbuf.stride(0), ptr(o), o.stride(1), o.stride(0), ptr(lse), B, H, Lq, D,
+         float(scale if scale is not None else D ** -0.5), float(score_bound), ptr(state), Lnew, window_tokens,
+         kbuf.shape[1], stream())
+    return o, lse
+
+
+def rope_rebase(kbuf, H, D, start, rows, cos, sin, old_off, new_off):
+    """In place: the `rows` live logical rows of the ring K buffer kbuf [B, cap, H D] (logical row i at
+    physical row (start + i) mod cap), stored rotated by table rows old_off + i, become the rotation of
+    table rows new_off + i (fp32 angle difference from the two table rows, one bf16 rounding)."""
+    assert kbuf.dim() == 3 and kbuf.shape[2] == H * D and kbuf.stride(2) == 1 and kbuf.dtype == BF16
+    assert cos.dtype == F32 and sin.dtype == F32 and cos.stride(1) == 1 and sin.stride(0) == cos.stride(0)
+    assert cos.shape[1] == D // 2
+    call("owlk_rope_rebase", ptr(kbuf), kbuf.stride(1), kbuf.stride(0), kbuf.shape[0], H, D, int(start), int(rows),
+         kbuf.shape[1], ptr(cos), ptr(sin), cos.stride(0), cos.shape[0], int(old_off), int(new_off), stream())
+
+
 def mm_qk_rope_fwd_kv(qkv0, qkv1, B, nf, n0, n1, H, D, cos, sin, tab_off, q_out, k_out, v_out):
     """MMDiT decode form: the two modalities' qkv GEMM outputs (qkv0 [B nf n0, 3 H D] video, qkv1
     [B nf n1, 3 H D] audio) -> rotated q of the joint frames [n0 video | n1 audio] into q_out

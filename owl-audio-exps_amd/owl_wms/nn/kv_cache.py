@@ -211,3 +211,131 @@ class SingleKVCache:
     @property
     def shape(self):
         return self.cache[0][0].shape
+
+
+class RingKVCache(SingleKVCache):
+    """Endless decode (sampling/stream.py FrameStream; the reference's inference/causvid_pipeline.py):
+    per layer a K/V ring ``[B, capacity, d]`` allocated once.  Logical row i of the live window lives at
+    physical row ``(start + i) % capacity``; writes behind the window and ``truncate(k, front=False)``
+    wrap, so neither the addresses nor the size ever change, however many frames pass through (a
+    captured HIP graph stays valid across wraps).  The decode kernels' ring forms follow the device
+    state vector {start, cached tokens, rope offset} (``owlk_qk_rope_fwd_kv_ring``,
+    ``owlk_attn_decode_ring_fwd``); ``rebase`` re-rotates the cached K to smaller RoPE positions
+    (``owlk_rope_rebase``), so the positions never leave the table either.
+
+    A wrapped window has no view: ``get`` / ``cache`` / ``extend`` return gathered copies."""
+
+    ring = True
+
+    def __init__(self, config, capacity, rope=None):
+        super().__init__(config)
+        assert capacity > 0
+        self.capacity = int(capacity)
+        self.rope = rope  # the model's RoPE table module (cos / sin), for rebase
+
+    def _alloc(self, i, like):
+        if self.bufs[i] is None:
+            self.bufs[i] = tuple(torch.empty(like.shape[0], self.capacity, like.shape[2], device=like.device,
+                                             dtype=like.dtype) for _ in range(2))
+
+    def _rows(self, i, first, n):
+        """physical rows of the logical rows first .. first + n - 1 of layer i's window"""
+        dev = self.bufs[i][0].device
+        return (torch.arange(first, first + n, device=dev) + self.start[i]) % self.capacity
+
+    def _views(self, i, n):
+        kb, vb = self.bufs[i]
+        idx = self._rows(i, 0, n)
+        return kb.index_select(1, idx), vb.index_select(1, idx)
+
+    def _reserve(self, i, need, like):
+        assert need <= self.capacity, f"ring capacity exceeded ({need} > {self.capacity} rows)"
+        self._alloc(i, like)
+
+    def enable_device_state(self, capacity=None):
+        """The position on the device (the ring decode kernels read it); the buffers already have their
+        final size, so this only creates the state vector."""
+        assert capacity is None or capacity <= self.capacity, "a ring cache does not grow"
+        assert all(b is not None for b in self.bufs), "enable_device_state after the context pass"
+        self.dev = torch.zeros(4, dtype=torch.int64, device=self.bufs[0][0].device)
+        self.sync_device_state()
+
+    def sync_device_state(self):
+        if self.dev is None:
+            return
+        st = {(self.start[i], self.len[i], self.offsets[i]) for i in range(self.config.n_layers)}
+        assert len(st) == 1, "device-state decode needs every layer at the same position"
+        s, n, o = st.pop()
+        assert 0 <= s < self.capacity and 0 <= n <= self.capacity
+        self.dev.copy_(torch.tensor([s, n, o, 0], dtype=torch.int64))
+
+    def commit_device(self, layer_ind, L):
+        assert self.len[layer_ind] + L <= self.capacity, "ring capacity exceeded (evict before committing)"
+        self.len[layer_ind] += L
+        self.offsets[layer_ind] += L
+
+    def extend_slots(self, layer_ind, L, like):
+        raise RuntimeError("RingKVCache: the new rows may wrap, so there is no slot view; the ring rope kernel "
+                           "(kernels.qk_rope_fwd_kv_ring) writes them")
+
+    def extended(self, layer_ind, L):
+        return self._views(layer_ind, self.len[layer_ind] + L)
+
+    def extend(self, layer_ind, new_k, new_v):
+        """new K/V written behind the window (wrapping); [cache | new] as gathered copies"""
+        assert self.noise_caches == 0.0, "extend reads the cache as stored (noise_caches must be 0)"
+        n, L = self.len[layer_ind], new_k.shape[1]
+        self._reserve(layer_ind, n + L, new_k)
+        kb, vb = self.bufs[layer_ind]
+        idx = self._rows(layer_ind, n, L)
+        kb.index_copy_(1, idx, new_k)
+        vb.index_copy_(1, idx, new_v)
+        return self._views(layer_ind, n + L)
+
+    def update(self, new_k, new_v, layer_ind):
+        """the layer's cache becomes (new_k, new_v), from row 0 (the context pass fills the ring)"""
+        assert self.bufs is not None, "Must reset cache before using"
+        L = new_k.shape[1]
+        assert L <= self.capacity, f"ring capacity exceeded ({L} > {self.capacity} rows)"
+        self._alloc(layer_ind, new_k)
+        self.offsets[layer_ind] += L - self.len[layer_ind]
+        kb, vb = self.bufs[layer_ind]
+        kb[:, :L].copy_(new_k)
+        vb[:, :L].copy_(new_v)
+        self.start[layer_ind], self.len[layer_ind] = 0, L
+
+    def truncate(self, truncate_amt, front=False):
+        amt = truncate_amt * self.config.tokens_per_frame
+        for i in range(self.config.n_layers):
+            amt_i = min(amt, self.len[i])
+            if not front:
+                self.start[i] = (self.start[i] + amt_i) % self.capacity
+            self.len[i] -= amt_i
+        self.sync_device_state()
+
+    def rebase(self, shift_tokens, rope=None):
+        """Lower every live key's RoPE position by `shift_tokens` (whole frames): each layer's cached K is
+        re-rotated in place (V carries no position), then the offsets drop.  Valid for tables whose
+        angles are linear in the frame index (MotionRoPE, Audio1DRoPE)."""
+        from .. import kernels as K
+        rope = rope if rope is not None else self.rope
+        assert rope is not None, "rebase needs the model's RoPE tables"
+        tpf = self.config.tokens_per_frame
+        assert shift_tokens >= 0 and shift_tokens % tpf == 0, "rebase by whole frames"
+        if shift_tokens == 0:
+            return
+        H = self.config.n_heads
+        D = self.config.d_model // H
+        for i in range(self.config.n_layers):
+            old = self.offsets[i] - self.len[i]
+            if old < shift_tokens:
+                raise RuntimeError(f"rebase by {shift_tokens} tokens would move the oldest cached key (position "
+                                   f"{old}) below 0")
+            if self.len[i]:
+                K.rope_rebase(self.bufs[i][0], H, D, self.start[i], self.len[i], rope.cos, rope.sin, old,
+                              old - shift_tokens)
+            self.offsets[i] -= shift_tokens
+        self.sync_device_state()
+
+    def clone(self):
+        raise RuntimeError("RingKVCache keeps fixed buffers; clone is not supported")

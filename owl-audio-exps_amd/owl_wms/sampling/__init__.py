@@ -1,7 +1,8 @@
 """Samplers (reference: owl_wms/sampling/__init__.py:1-39).
 
 Implemented on libowlk's KV-cache decode path: ``av_caching`` (AVCachingSamplerV2, the registry
-entry the reference resolves it to), ``audio_caching``, and the audio + video core's samplers
+entry the reference resolves it to), ``av_stream`` (stream.py: the same sampler on a ring cache with a
+RoPE rebase, for rollouts past ``n_frames``), ``audio_caching``, and the audio + video core's samplers
 ``av_window`` / ``av_causal`` / ``av_causal_no_cfg`` (av_window.py; the causal ones decode on the
 MMDiT's fused joint-frame path).  The one-step variant is outside this build's scope (SURVEY.md
 §8(f); the reference's import of it is broken).
@@ -16,6 +17,9 @@ def get_sampler_cls(sampler_id):
     if sampler_id == "av_caching":
         from .av_caching_v2 import AVCachingSamplerV2
         return AVCachingSamplerV2
+    if sampler_id == "av_stream":
+        from .stream import StreamSampler
+        return StreamSampler
     if sampler_id == "audio_caching":
         from .audio_caching import AudioCachingSampler
         return AudioCachingSampler
