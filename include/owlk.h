@@ -187,6 +187,19 @@ int owlk_mm_qk_rope_fwd_kv(const void* qkv0, long ld0, const void* qkv1, long ld
                            int H, int D, const float* cosb, const float* sinb, long ld_tab, long n_tab,
                            long tab_off, void* qo, long ldqo, long sqo, void* ko, long ldko, long sko, void* vo,
                            long ldvo, long svo, void* stream);
+/* Ring form of owlk_mm_qk_rope_fwd_kv for endless audio + video streaming (the reference's
+ * inference/causvid_pipeline.py: pipe(new_mouse, new_btn) -> frame; mmattn.py:46-86 cache branch): the
+ * position is on the device, state = {start, cached tokens, rope offset} (int64), and kbuf / vbuf are
+ * whole ring buffers [B, cap, H D].  With L = nf (n0 + n1), token t of a batch reads table row
+ * offset + t -- the absolute position, not the cached length mmattn.py:60-62 ropes at, which collides
+ * with live keys after an eviction -- and writes k / v to row (start + cached + t) mod cap; each token
+ * wraps on its own.  The per-row arithmetic is owlk_mm_qk_rope_fwd_kv's.  Contract: 0 <= start < cap,
+ * cached >= 0, cached + L <= cap, 0 <= offset, offset + L <= n_tab; outside it every q row becomes NaN
+ * and neither the cache nor the table is touched. */
+int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf, int n0,
+                                int n1, int H, int D, const float* cosb, const float* sinb, long ld_tab, long n_tab,
+                                const long* state, void* qo, long ldqo, long sqo, void* kbuf, long ldk, long skb,
+                                void* vbuf, long ldv, long svb, long cap, void* stream);
 int owlk_qk_rope_bwd(const void* dqk, long ldd, const void* qkv, long ldq, long T, int H, int D,
                      const float* cosb, const float* sinb, long ld_tab, long n_tab, long tab_off, long tpos_div,
                      const float* rstd, void* dqkv, long ldg, void* stream);
@@ -249,6 +262,20 @@ int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, const void* k,
                                long ldv, long svb, void* o0, long ldo0, void* o1, long ldo1, float* lse, long B,
                                int H, int n0, int n1, long Lkv, int head_dim, float scale, float score_bound,
                                void* stream);
+/* Ring form of owlk_attn_decode_joint_fwd for endless audio + video streaming (the reference's
+ * inference/causvid_pipeline.py on the mmattn.py:46-86 cache branch): the key range comes from the device
+ * state {start, cached tokens, rope offset} over ring buffers kbuf / vbuf [B, cap, H D] (the new frame's
+ * rows written there first, owlk_mm_qk_rope_fwd_kv_ring).  total = cached + n0 + n1; first = total -
+ * window_tokens where window_tokens > 0 and total > window_tokens, else 0; Lkv = total - first; logical
+ * key i lives at physical row (start + first + i) mod cap.  Same tile decomposition as the linear
+ * kernel (each DMA row's address wraps), so o0, o1 and lse equal owlk_attn_decode_joint_fwd's on an
+ * unrolled copy of the buffers bit for bit.  Contract: 0 <= start < cap, cached >= 0, total <= cap;
+ * outside it NaN o0 / o1 rows and lse, nothing read.  head_dim 64, n0 + n1 <= 80, bounded softmax only. */
+int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                    const void* vbuf, long ldv, long svb, void* o0, long ldo0, void* o1, long ldo1,
+                                    float* lse, long B, int H, int n0, int n1, int head_dim, float scale,
+                                    float score_bound, const long* state, long window_tokens, long cap,
+                                    void* stream);
 /* delta[b, h, t] = sum_d dO * O (fp32), the backward's row constant */
 int owlk_attn_delta(const void* o, const void* dout, long ld, long B, long L, int H, int D, float* delta,
                     void* stream);

@@ -20,6 +20,7 @@
 #include "attn_fwd4.hpp"
 
 #include <cstdlib>
+#include <type_traits>
 
 
 namespace {
@@ -991,9 +992,50 @@ struct JointCfg {
   static constexpr int SMEM = 4 * C::RING > COMB ? 4 * C::RING : COMB;
 };
 
-__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointP p) {
+// RING (owlk_attn_decode_joint_ring_fwd): p.k / p.v are rings of cap rows and the key range comes from the
+// device state {start, cached tokens, rope offset}: total = cached + Lq keys, the last wtok of them on a
+// windowed layer (wtok > 0), logical key i of the visible range at physical row (start + first + i) mod
+// cap.  The tile decomposition stays the logical one (tile w + 4 i of wave w from the first visible key),
+// only each DMA row's source address wraps (tile_glds_ring), so o0, o1 and lse equal the linear kernel's
+// on an unrolled copy of the buffers bit for bit.  Outside the contract nothing is read and the rows
+// become NaN (attn_fwd16_split_k's guard).
+struct JointRingP : JointP {
+  const long* state;  // {start, cached tokens, rope offset}
+  long wtok, cap;
+};
+template <bool RING>
+using JointArg = std::conditional_t<RING, JointRingP, JointP>;
+
+template <bool RING = false>
+__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING> p) {
   using C = DecCfg<64>;
   constexpr int D = 64, KTD = C::KTD, NQT = JointCfg::NQT, QR = JointCfg::QR;
+  long org = 0, cap = 0;
+  if constexpr (RING) {
+    cap = p.cap;
+    const long start = p.state[0], cached = p.state[1], total = cached + p.Lq, wtok = p.wtok;
+    if (start < 0 || start >= cap || cached < 0 || total > cap) {
+      const long b = blockIdx.z;
+      const int head = blockIdx.y;
+      bf16x8 nan8;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) nan8[e] = (bf16)NAN;
+      for (int item = threadIdx.x; item < 4 * QR; item += 256) {
+        const int q = item >> 2, d0 = 16 * (item & 3);
+        if (q >= p.Lq) continue;
+        bf16* O =
+            (q < p.n0 ? p.o0 + (b * p.n0 + q) * p.ldo0 : p.o1 + (b * p.n1 + (q - p.n0)) * p.ldo1) + head * D + d0;
+        *(bf16x8*)O = nan8;
+        *(bf16x8*)(O + 8) = nan8;
+        if ((item & 3) == 0 && p.lse) p.lse[(b * p.H + head) * p.Lq + q] = NAN;
+      }
+      return;
+    }
+    const long first = wtok > 0 && total > wtok ? total - wtok : 0;
+    p.Lkv = total - first;
+    org = start + first;  // start < cap, first < total <= cap: one wrap at most
+    org = org < cap ? org : org - cap;
+  }
   __shared__ __attribute__((aligned(16))) char smem[JointCfg::SMEM];
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int c = lane & 15, g = lane >> 4;
@@ -1034,8 +1076,13 @@ __global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointP p) {
     char* buf = ring + (i & 1) * C::TILEB;
 #pragma unroll
     for (int q4 = 0; q4 < KTD / 16; ++q4) {
-      tile_glds<SW_ROW>(buf, K, p.ldk, c0, p.Lkv, q4, lane);
-      tile_glds<SW_DUAL>(buf + C::SUBK, V, p.ldv, c0, p.Lkv, q4, lane);
+      if constexpr (RING) {
+        tile_glds_ring<SW_ROW>(buf, K, p.ldk, c0, p.Lkv, org, cap, q4, lane);
+        tile_glds_ring<SW_DUAL>(buf + C::SUBK, V, p.ldv, c0, p.Lkv, org, cap, q4, lane);
+      } else {
+        tile_glds<SW_ROW>(buf, K, p.ldk, c0, p.Lkv, q4, lane);
+        tile_glds<SW_DUAL>(buf + C::SUBK, V, p.ldv, c0, p.Lkv, q4, lane);
+      }
     }
   };
   if (nt > 0) issue(0);
@@ -1350,6 +1397,46 @@ extern "C" int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, con
   p.ldq = ldq; p.sqb = sqb; p.ldk = ldk; p.skb = skb; p.ldv = ldv; p.svb = svb; p.ldo0 = ldo0; p.ldo1 = ldo1;
   p.Lq = (long)n0 + n1; p.Lkv = Lkv; p.n0 = n0; p.n1 = n1; p.H = H;
   p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL(attn_decode_joint_k, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL(attn_decode_joint_k<false>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                     p);
   return owlk::check_launch("attn_decode_joint_fwd");
+}
+
+// Ring form for endless audio + video streaming (the reference's inference/causvid_pipeline.py: pipe(new_mouse,
+// new_btn) -> frame, on the mmattn.py:46-86 cache branch): owlk_attn_decode_joint_fwd with the key range
+// taken from the device state {start, cached tokens, rope offset} over ring buffers kbuf / vbuf [B, cap,
+// H D].  total = cached + n0 + n1 keys; a windowed layer (window_tokens > 0) sees the last window_tokens
+// of them; logical key i of the visible range lives at physical row (start + first + i) mod cap.  The
+// same bits as the linear entry on an unrolled copy of the buffers.  Contract: 0 <= start < cap,
+// cached >= 0, total <= cap; outside it NaN o0 / o1 rows and lse, nothing read.
+extern "C" int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                               long skb, const void* vbuf, long ldv, long svb, void* o0, long ldo0,
+                                               void* o1, long ldo1, float* lse, long B, int H, int n0, int n1,
+                                               int head_dim, float scale, float score_bound, const long* state,
+                                               long window_tokens, long cap, void* stream) {
+  OWLK_REQUIRE(head_dim == 64, "attn_decode_joint_ring_fwd: head_dim %d not built (64)", head_dim);
+  OWLK_REQUIRE(B > 0 && H > 0 && n0 > 0 && n1 > 0 && B <= 65535 && H <= 65535 && state && window_tokens >= 0,
+               "attn_decode_joint_ring_fwd: bad sizes");
+  OWLK_REQUIRE((long)n0 + n1 <= JointCfg::QR,
+               "attn_decode_joint_ring_fwd: one joint frame of at most %d rows (got %ld)", JointCfg::QR,
+               (long)n0 + n1);
+  OWLK_REQUIRE(cap >= (long)n0 + n1, "attn_decode_joint_ring_fwd: cache capacity %ld rows", cap);
+  OWLK_REQUIRE(score_bound > 0.f && score_bound * scale < 40.f, "attn_decode_joint_ring_fwd: needs a score bound");
+  OWLK_REQUIRE(((uintptr_t)q | (uintptr_t)kbuf | (uintptr_t)vbuf | (uintptr_t)o0 | (uintptr_t)o1) % 16 == 0 &&
+                   ldq % 8 == 0 && ldk % 8 == 0 && ldv % 8 == 0 && ldo0 % 8 == 0 && ldo1 % 8 == 0 && sqb % 8 == 0 &&
+                   skb % 8 == 0 && svb % 8 == 0,
+               "attn_decode_joint_ring_fwd: q/k/v/o rows must be 16-byte aligned");
+  const long hd = (long)H * head_dim;
+  OWLK_REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo0 >= hd && ldo1 >= hd,
+               "attn_decode_joint_ring_fwd: a row stride is shorter than its H * head_dim columns");
+  JointRingP p;
+  p.state = state; p.wtok = window_tokens; p.cap = cap;
+  p.q = (const bf16*)q; p.k = (const bf16*)kbuf; p.v = (const bf16*)vbuf;
+  p.o0 = (bf16*)o0; p.o1 = (bf16*)o1; p.lse = lse;
+  p.ldq = ldq; p.sqb = sqb; p.ldk = ldk; p.skb = skb; p.ldv = ldv; p.svb = svb; p.ldo0 = ldo0; p.ldo1 = ldo1;
+  p.Lq = (long)n0 + n1; p.Lkv = 0; p.n0 = n0; p.n1 = n1; p.H = H;  // Lkv from the device state
+  p.scale_log2 = scale * LOG2E;
+  hipLaunchKernelGGL(attn_decode_joint_k<true>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
+                     p);
+  return owlk::check_launch("attn_decode_joint_ring_fwd");
 }

@@ -511,14 +511,16 @@ __global__ __launch_bounds__(256) void rope_rebase_k(bf16* __restrict__ kbuf, lo
 // r < n0) or the audio one (row (bb nf + f) n1 + r - n0); table row tab_off + f (n0 + n1) + r.  The
 // arithmetic per (token, q|k, head) row is qk_rope_fwd_k's, statement for statement, so q, k, v equal
 // frame_interleave -> qk_rope_fwd -> cache copy bit for bit.
-template <int D>
-__global__ __launch_bounds__(256) void mm_qk_rope_kv_k(const bf16* __restrict__ qkv0, long ld0,
-                                                       const bf16* __restrict__ qkv1, long ld1, long B, long nf,
-                                                       int n0, int n1, int H, const float* __restrict__ cosb,
-                                                       const float* __restrict__ sinb, long ld_tab, long tab_off,
-                                                       bf16* __restrict__ qo, long ldqo, long sqo,
-                                                       bf16* __restrict__ ko, long ldko, long sko,
-                                                       bf16* __restrict__ vo, long ldvo, long svo) {
+// RING (owlk_mm_qk_rope_fwd_kv_ring): ko / vo are whole ring buffers of cap rows and the position comes
+// from the device state {start, cached tokens, rope offset}: table row offset + t, token t's k / v at
+// row (start + cached + t) mod cap (each token wraps on its own: a 65-row frame straddles the end).
+// Outside the contract (qk_rope_kv_k's guard) q rows become NaN, cache and table are not touched.
+template <int D, bool RING>
+DEV void mm_qk_rope_kv_body(const bf16* __restrict__ qkv0, long ld0, const bf16* __restrict__ qkv1, long ld1, long B,
+                            long nf, int n0, int n1, int H, const float* __restrict__ cosb,
+                            const float* __restrict__ sinb, long ld_tab, long tab_off, bf16* __restrict__ qo,
+                            long ldqo, long sqo, bf16* __restrict__ ko, long ldko, long sko, bf16* __restrict__ vo,
+                            long ldvo, long svo, const long* __restrict__ state, long n_tab, long cap) {
   constexpr int CPR = D / 8;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long rowid = gid / CPR;  // (token, which, head)
@@ -528,6 +530,22 @@ __global__ __launch_bounds__(256) void mm_qk_rope_kv_k(const bf16* __restrict__ 
   const long tok = rowid / (3 * H);
   const int wh = rowid % (3 * H);  // which * H + head
   const long bb = tok / L, t = tok - bb * L;
+  if constexpr (RING) {
+    const long start = state[0], cached = state[1], off = state[2];
+    if (start < 0 || start >= cap || cached < 0 || cached + L > cap || off < 0 || off + L > n_tab) {
+      if (wh < H) {
+        const bf16x4 nan4 = {(bf16)NAN, (bf16)NAN, (bf16)NAN, (bf16)NAN};
+        bf16* o = qo + bb * sqo + t * ldqo + (long)wh * D;
+        *(bf16x4*)(o + j * 4) = nan4;
+        *(bf16x4*)(o + D / 2 + j * 4) = nan4;
+      }
+      return;
+    }
+    const long pr0 = start + cached + t, pr = pr0 < cap ? pr0 : pr0 - cap;  // start + cached < 2 cap - L
+    ko += (pr - t) * ldko;
+    vo += (pr - t) * ldvo;
+    tab_off = off;
+  }
   const long f = t / tpf, r = t - f * tpf;
   const bf16* src = r < n0 ? qkv0 + ((bb * nf + f) * n0 + r) * ld0 : qkv1 + ((bb * nf + f) * n1 + (r - n0)) * ld1;
   const bf16x8 v = *(const bf16x8*)(src + (long)wh * D + j * 8);
@@ -556,6 +574,31 @@ __global__ __launch_bounds__(256) void mm_qk_rope_kv_k(const bf16* __restrict__ 
   bf16* o = wh < H ? qo + bb * sqo + t * ldqo + (long)wh * D : ko + bb * sko + t * ldko + (long)(wh - H) * D;
   *(bf16x4*)(o + j * 4) = y0;
   *(bf16x4*)(o + D / 2 + j * 4) = y1;
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void mm_qk_rope_kv_k(const bf16* __restrict__ qkv0, long ld0,
+                                                       const bf16* __restrict__ qkv1, long ld1, long B, long nf,
+                                                       int n0, int n1, int H, const float* __restrict__ cosb,
+                                                       const float* __restrict__ sinb, long ld_tab, long tab_off,
+                                                       bf16* __restrict__ qo, long ldqo, long sqo,
+                                                       bf16* __restrict__ ko, long ldko, long sko,
+                                                       bf16* __restrict__ vo, long ldvo, long svo) {
+  mm_qk_rope_kv_body<D, false>(qkv0, ld0, qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, tab_off, qo, ldqo, sqo, ko,
+                               ldko, sko, vo, ldvo, svo, nullptr, 0, 0);
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void mm_qk_rope_kv_ring_k(const bf16* __restrict__ qkv0, long ld0,
+                                                            const bf16* __restrict__ qkv1, long ld1, long B, long nf,
+                                                            int n0, int n1, int H, const float* __restrict__ cosb,
+                                                            const float* __restrict__ sinb, long ld_tab,
+                                                            bf16* __restrict__ qo, long ldqo, long sqo,
+                                                            bf16* __restrict__ kbuf, long ldk, long skb,
+                                                            bf16* __restrict__ vbuf, long ldv, long svb,
+                                                            const long* __restrict__ state, long n_tab, long cap) {
+  mm_qk_rope_kv_body<D, true>(qkv0, ld0, qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, 0, qo, ldqo, sqo, kbuf, ldk,
+                              skb, vbuf, ldv, svb, state, n_tab, cap);
 }
 
 // backward: d(q_rot) -> inverse rotation -> rms_norm backward (recomputing xhat from raw qkv)
@@ -1114,6 +1157,48 @@ extern "C" int owlk_mm_qk_rope_fwd_kv(const void* qkv0, long ld0, const void* qk
                        (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, tab_off, (bf16*)qo, ldqo, sqo,
                        (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo);
   return owlk::check_launch("mm_qk_rope_fwd_kv");
+}
+
+// Ring form for endless audio + video streaming (the reference's inference/causvid_pipeline.py: pipe(new_mouse,
+// new_btn) -> frame, on the mmattn.py:46-86 cache branch): owlk_mm_qk_rope_fwd_kv with the position on the
+// device, state = {start, cached tokens, rope offset}.  Token t of a batch reads table row offset + t (the
+// absolute position, not the cached length: after an eviction the two differ) and writes k / v to row
+// (start + cached + t) mod cap of the ring buffers kbuf / vbuf [B, cap, H D].  Contract: 0 <= start < cap,
+// cached >= 0, cached + L <= cap, 0 <= offset, offset + L <= n_tab (L = nf (n0 + n1)); outside it NaN q rows,
+// cache and table untouched.
+extern "C" int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf,
+                                           int n0, int n1, int H, int D, const float* cosb, const float* sinb,
+                                           long ld_tab, long n_tab, const long* state, void* qo, long ldqo, long sqo,
+                                           void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
+                                           void* stream) {
+  OWLK_REQUIRE(D == 64 || D == 128, "mm_qk_rope_fwd_kv_ring: head_dim %d unsupported", D);
+  OWLK_REQUIRE(B > 0 && nf > 0 && n0 > 0 && n1 > 0 && H > 0,
+               "mm_qk_rope_fwd_kv_ring: bad sizes B=%ld nf=%ld n0=%d n1=%d", B, nf, n0, n1);
+  OWLK_REQUIRE(state, "mm_qk_rope_fwd_kv_ring: state pointer required");
+  const long L = nf * ((long)n0 + n1);
+  OWLK_REQUIRE(n_tab >= L && cap >= L,
+               "mm_qk_rope_fwd_kv_ring: %ld new rows need a rope table (%ld rows) and a ring (%ld rows) that hold them",
+               L, n_tab, cap);
+  OWLK_REQUIRE(ld0 >= 3L * H * D && ld1 >= 3L * H * D && ldqo >= (long)H * D && ldk >= (long)H * D &&
+                   ldv >= (long)H * D,
+               "mm_qk_rope_fwd_kv_ring: a row stride is shorter than its row");
+  OWLK_REQUIRE(((uintptr_t)qkv0 | (uintptr_t)qkv1) % 16 == 0 && ld0 % 8 == 0 && ld1 % 8 == 0,
+               "mm_qk_rope_fwd_kv_ring: qkv rows must be 16-byte aligned");
+  OWLK_REQUIRE(((uintptr_t)qo | (uintptr_t)kbuf | (uintptr_t)vbuf) % 16 == 0 && ldqo % 8 == 0 && ldk % 8 == 0 &&
+                   ldv % 8 == 0 && sqo % 8 == 0 && skb % 8 == 0 && svb % 8 == 0,
+               "mm_qk_rope_fwd_kv_ring: destinations must be 16-byte aligned");
+  const long threads = B * L * 3 * H * (D / 8);
+  OWLK_REQUIRE(threads < (1L << 31) * 256, "mm_qk_rope_fwd_kv_ring: too many rows for one launch");
+  dim3 g((unsigned)((threads + 255) / 256));
+  if (D == 64)
+    hipLaunchKernelGGL(mm_qk_rope_kv_ring_k<64>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
+                       (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, (bf16*)qo, ldqo, sqo,
+                       (bf16*)kbuf, ldk, skb, (bf16*)vbuf, ldv, svb, state, n_tab, cap);
+  else
+    hipLaunchKernelGGL(mm_qk_rope_kv_ring_k<128>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
+                       (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, (bf16*)qo, ldqo, sqo,
+                       (bf16*)kbuf, ldk, skb, (bf16*)vbuf, ldv, svb, state, n_tab, cap);
+  return owlk::check_launch("mm_qk_rope_fwd_kv_ring");
 }
 
 extern "C" int owlk_qk_rope_bwd(const void* dqk, long ldd, const void* qkv, long ldq, long T, int H, int D,

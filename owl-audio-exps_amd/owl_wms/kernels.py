@@ -442,6 +442,55 @@ def attn_decode_joint_fwd(q, k, v, H, D, n0, n1, scale=None, score_bound=0.0, wa
     return o0, o1, lse
 
 
+def _ring_state(state, kbuf, vbuf, B, H, D):
+    assert state.dtype == torch.int64 and state.numel() >= 3 and state.is_cuda
+    for t in (kbuf, vbuf):
+        assert t.dim() == 3 and t.shape[0] == B and t.shape[2] == H * D and t.stride(2) == 1 and t.dtype == BF16
+    assert kbuf.shape[1] == vbuf.shape[1], "ring buffers of one capacity"
+
+
+def mm_qk_rope_fwd_kv_ring(qkv0, qkv1, B, nf, n0, n1, H, D, cos, sin, state, q_out, kbuf, vbuf):
+    """mm_qk_rope_fwd_kv with the position on the device (state int64 {start, cached, offset}) and ring
+    destinations: token t of the joint frames reads table row offset + t and writes k / v to row
+    (start + cached + t) mod cap of kbuf / vbuf [B, cap, H D] (RingKVCache); 0 <= start < cap,
+    cached + L <= cap and offset + L inside the table, else NaN q rows and an untouched cache."""
+    L = nf * (n0 + n1)
+    for t, rows, nm in ((qkv0, B * nf * n0, "qkv0"), (qkv1, B * nf * n1, "qkv1")):
+        assert t.dim() == 2 and t.shape == (rows, 3 * H * D) and t.stride(1) == 1 and t.dtype == BF16, nm
+    assert q_out.shape == (B, L, H * D) and q_out.stride(2) == 1 and q_out.dtype == BF16, "q_out"
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    assert cos.stride(1) == 1 and sin.stride(0) == cos.stride(0) and cos.shape[1] * 2 == D
+    call("owlk_mm_qk_rope_fwd_kv_ring", ptr(qkv0), qkv0.stride(0), ptr(qkv1), qkv1.stride(0), B, nf, n0, n1, H, D,
+         ptr(cos), ptr(sin), cos.stride(0), cos.shape[0], ptr(state), ptr(q_out), q_out.stride(1), q_out.stride(0),
+         ptr(kbuf), kbuf.stride(1), kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), kbuf.shape[1], stream())
+
+
+def attn_decode_joint_ring_fwd(q, kbuf, vbuf, H, D, n0, n1, state, window_tokens=0, scale=None, score_bound=0.0,
+                               want_lse=False, o0=None, o1=None):
+    """attn_decode_joint_fwd on ring buffers with the key range from the device state: q [B, n0 + n1, H D]
+    against the logical keys [cache | this frame] (or their last window_tokens), logical key i at physical
+    row (start + first + i) mod cap; the same bits as attn_decode_joint_fwd on an unrolled copy of the
+    buffers -> (o0, o1, lse or None)."""
+    _v3(q, "q")
+    B, Lq = q.shape[0], q.shape[1]
+    assert decode_joint_supported(D, n0, n1) and Lq == n0 + n1, \
+        f"attn_decode_joint_ring_fwd: head_dim {D} / frame of {n0} + {n1} rows not supported"
+    assert q.shape[2] >= H * D
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    if o0 is None:
+        o0 = torch.empty(B * n0, H * D, device=q.device, dtype=BF16)
+    if o1 is None:
+        o1 = torch.empty(B * n1, H * D, device=q.device, dtype=BF16)
+    _rowmajor(o0, "o0"), _rowmajor(o1, "o1")
+    assert o0.shape == (B * n0, H * D) and o1.shape == (B * n1, H * D)
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32) if want_lse else None
+    call("owlk_attn_decode_joint_ring_fwd", ptr(q), q.stride(1), q.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), ptr(o0), o0.stride(0), ptr(o1), o1.stride(0),
+         ptr(lse), B, H, n0, n1, D, float(scale if scale is not None else D ** -0.5), float(score_bound), ptr(state),
+         int(window_tokens), kbuf.shape[1], stream())
+    return o0, o1, lse
+
+
 def qk_rope_bwd(dqk, qkv, rstd, H, D, cos, sin, dqkv, tab_off=0, tpos_div=0, dbias=None):
     """-> dqkv[:, :2HD]; with dbias (fp32 [2HD]) also dbias += column sums of those outputs (the q / k
     part of the qkv bias gradient), fused into the same pass where the shape allows."""

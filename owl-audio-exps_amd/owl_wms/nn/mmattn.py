@@ -25,11 +25,15 @@ With MMDIT.enable_decoding() (off by default; the causal audio + video samplers 
 their decode steps) a cached call at head_dim 64 takes MMDiTBlock._forward_decode: the rope kernel reads
 the two qkv outputs and writes k / v straight into the cache (no interleave, no extend copies), and one
 new frame runs the joint decode attention with the video / audio rows written apart (no split).
+A RingKVCache past its context pass (sampling/stream.py AVFrameStream) takes MMDiTBlock._forward_ring_decode:
+the same launch list on the two kernels' ring forms, the position read from the cache's device vector and
+the new rows roped at the absolute offset.
 """
 import torch
 from torch import nn
 
 from .. import kernels as K
+from .attn import check_rope_rows
 from .fused import (bf16_weight, bgrad_into, block_head_bwd, block_tail, block_tail_bwd, cond_silu, grad_done, linear,
                     wgrad_into)
 from .mlp import MLP
@@ -281,6 +285,8 @@ class MMDiTBlock(nn.Module):
     def forward(self, x0, x1, cond0, cond1, block_mask=None, kv_cache=None):
         if kv_cache is not None:
             with torch.no_grad():
+                if getattr(kv_cache, "ring", False) and kv_cache.get_offset(self.attn.layer_idx) > 0:
+                    return self._forward_ring_decode(x0, x1, cond0, cond1, block_mask, kv_cache)
                 if self.decoding and self._decode_ok(block_mask, kv_cache):
                     return self._forward_decode(x0, x1, cond0, cond1, block_mask, kv_cache)
                 return self._forward_cached(x0, x1, cond0, cond1, block_mask, kv_cache)
@@ -347,7 +353,8 @@ class MMDiTBlock(nn.Module):
         cache read as stored with slots to write into."""
         cfg = self.config
         return cfg.d_model // cfg.n_heads == 64 and block_mask is not None and block_mask.causal and \
-            block_mask.arrays is None and kv_cache.noise_caches == 0.0 and hasattr(kv_cache, "extend_slots")
+            block_mask.arrays is None and kv_cache.noise_caches == 0.0 and hasattr(kv_cache, "extend_slots") and \
+            not getattr(kv_cache, "ring", False)  # a ring's new rows may wrap: no slot views (_forward_ring_decode)
 
     def _forward_decode(self, x0, x1, cond0, cond1, block_mask, kv_cache):
         """_forward_cached with the joint frames never assembled (MMDIT.enable_decoding): the rope kernel
@@ -394,6 +401,49 @@ class MMDiTBlock(nn.Module):
         outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
         return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
 
+    def _forward_ring_decode(self, x0, x1, cond0, cond1, block_mask, kv_cache):
+        """One new joint frame against a RingKVCache (sampling/stream.py AVFrameStream): _forward_decode's
+        launch list -- AdaLN x 2, qkv GEMM x 2, rope, joint attention, block_tail x 2 -- on the ring forms of
+        the two joint-frame kernels (kernels.mm_qk_rope_fwd_kv_ring, kernels.attn_decode_joint_ring_fwd).
+        They read {start, cached tokens, rope offset} from the cache's device vector, so nothing here
+        depends on a host position and a captured step stays valid across frames, wraps and rebases.
+        The new rows are roped at the ABSOLUTE offset (the vector's third word), not at the cached length
+        _forward_cached / _forward_decode use as mmattn.py:60-62 does: after an eviction the cached length
+        points at positions live keys already hold."""
+        cfg, a = self.config, self.attn
+        d, H = cfg.d_model, cfg.n_heads
+        D = d // H
+        n0, n1 = cfg.sample_size ** 2, 1
+        B, T0, _ = x0.shape
+        nf = T0 // n0
+        if nf != 1 or D != 64 or kv_cache.dev is None or kv_cache.noise_caches != 0.0 or \
+                not K.decode_joint_supported(D, n0, n1) or K.qk_norm_bound(D) <= 0.0:
+            raise RuntimeError("a RingKVCache decodes one joint frame at a time on the device-state path (head_dim "
+                               f"64, at most {K.JOINT_DECODE_ROWS} rows, noise_caches 0, enable_device_state() after "
+                               f"the context pass; got {nf} frame(s) of {n0} + {n1} rows, head_dim {D}, noise_caches "
+                               f"{kv_cache.noise_caches}, device state {'on' if kv_cache.dev is not None else 'off'})")
+        T = n0 + n1
+        ns = (n0, n1)
+        xs = (x0.reshape(-1, d).to(BF16).contiguous(), x1.reshape(-1, d).to(BF16).contiguous())
+        ms = (cond0.reshape(B * nf, 6 * d), cond1.reshape(B * nf, 6 * d))
+        qkv = []
+        for s in range(2):
+            h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
+            wqkv, bqkv = self.qkv_params(s)
+            qkv.append(K.gemm(h, bf16_weight(wqkv), bias=bqkv))
+        li = a.layer_idx
+        kb, vb = kv_cache.bufs[li]
+        q = torch.empty(B, T, d, device=x0.device, dtype=BF16)
+        K.mm_qk_rope_fwd_kv_ring(qkv[0], qkv[1], B, nf, n0, n1, H, D, a.rope.cos, a.rope.sin, kv_cache.dev, q, kb, vb)
+        del qkv
+        window = block_mask.window if block_mask is not None else None
+        os_ = K.attn_decode_joint_ring_fwd(q, kb, vb, H, D, n0, n1, kv_cache.dev, int(window) * T if window else 0,
+                                           score_bound=K.qk_norm_bound(D))[:2]
+        if kv_cache.should_update:
+            kv_cache.commit_device(li, T)
+        outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
+        return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
+
 
 class MMDIT(nn.Module):
     def __init__(self, config):
@@ -431,6 +481,13 @@ class MMDIT(nn.Module):
         lin = self.cond_proj[1]
         c = linear(cond_silu(cond), lin.weight, lin.bias)
         cond0, cond1 = c.chunk(2, dim=-1)
+        ring = getattr(kv_cache, "ring", False)
+        if ring:
+            # the ring kernels read the position from the device and would only poison the rows with NaN:
+            # check it on the host first, as the reference's short table slice fails (attn.check_rope_rows)
+            check_rope_rows(self.rope, kv_cache.get_offset(0), x1.shape[1] * self.config.tokens_per_frame)
         for i, block in enumerate(self.blocks):
             x0, x1 = block(x0, x1, cond0, cond1, local_mask if self.local_layers[i] else global_mask, kv_cache)
+        if ring and kv_cache.should_update:
+            kv_cache.sync_device_state()  # every layer committed the frame
         return x0, x1

@@ -4,13 +4,16 @@ Implemented on libowlk's KV-cache decode path: ``av_caching`` (AVCachingSamplerV
 entry the reference resolves it to), ``av_stream`` (stream.py: the same sampler on a ring cache with a
 RoPE rebase, for rollouts past ``n_frames``), ``audio_caching``, and the audio + video core's samplers
 ``av_window`` / ``av_causal`` / ``av_causal_no_cfg`` (av_window.py; the causal ones decode on the
-MMDiT's fused joint-frame path).  The one-step variant is outside this build's scope (SURVEY.md
+MMDiT's fused joint-frame path) and ``av_audio_stream`` (stream.py AVStreamSampler: endless audio + video
+streaming on a ring cache, each frame cached once).  The one-step variant is outside this build's scope (SURVEY.md
 §8(f); the reference's import of it is broken).
 """
 
 # the samplers that take the (video, audio) core: sampler(model, video, audio, mouse, btn)
 AV_WINDOW_SAMPLERS = {"av_window": "AVWindowSampler", "av_causal": "CausalAVWindowSampler",
                       "av_causal_no_cfg": "CausalAVWindowSamplerNoCFG"}
+# every sampler with that call signature (AVRFTTrainer's eval step takes any of them)
+AV_CORE_SAMPLERS = tuple(AV_WINDOW_SAMPLERS) + ("av_audio_stream",)
 
 
 def get_sampler_cls(sampler_id):
@@ -20,6 +23,9 @@ def get_sampler_cls(sampler_id):
     if sampler_id == "av_stream":
         from .stream import StreamSampler
         return StreamSampler
+    if sampler_id == "av_audio_stream":
+        from .stream import AVStreamSampler
+        return AVStreamSampler
     if sampler_id == "audio_caching":
         from .audio_caching import AudioCachingSampler
         return AudioCachingSampler

@@ -25,7 +25,7 @@ import torch.distributed as dist
 from ..data import get_loader
 from ..models import get_model_cls
 from ..muon import FusedAdamW, init_muon
-from ..sampling import AV_WINDOW_SAMPLERS, get_sampler_cls
+from ..sampling import AV_CORE_SAMPLERS, get_sampler_cls
 from ..schedulers import get_scheduler_cls
 from ..utils import Timer, batch_permute_to_length, strip_prefixes
 from ..utils.grad_reducer import EMA, GradReducer
@@ -254,7 +254,7 @@ class AVRFTTrainer(RFTTrainer):
     def eval_setup(self):
         """av_trainer.py:208-221: the samplers that take the (video, audio) core; any other sampler_id
         (or none) samples nothing."""
-        if self.train_cfg.get("sampler_id") not in AV_WINDOW_SAMPLERS:
+        if self.train_cfg.get("sampler_id") not in AV_CORE_SAMPLERS:
             return None, None
         return super().eval_setup()
 
