@@ -392,6 +392,32 @@ long owlk_critic_loss_ws_bytes(long n);
 int owlk_critic_loss(const void* pred, int pred_f32, const void* z, const void* video, int in_f32,
                      const void* mask, long B, long N, long F, float gscale, float* loss, void* dpred, void* ws,
                      long ws_bytes, void* stream);
+/* ---- CausVid distillation tails (csrc/distill.hip), under the rules of the self-forcing ones above: [B, N, F]
+ * tensors, F % 8 == 0, 16-B aligned, the latents bf16 (in_f32 = 0) or fp32 (1) and so the velocities (v_f32);
+ * ts, ts_full fp32 [B, N]; mask one byte per frame; fp32 arithmetic from the loaded values, one rounding on
+ * the store; no atomics, the same bits on every call.
+ *
+ * The noising of the rollout (causvid_vid_only.py:142-147) and of both losses (:191-196, :232-237):
+ * t = mask[f] ? ts[f] : noise_prev (mask NULL: t = ts[f], the losses' lerp_batched); noisy = x (1 - t) + z t
+ * in x's dtype; ts_full[f] = t (ts_full NULL: not written). */
+int owlk_causvid_mix(const void* x, const void* z, int in_f32, const float* ts, const void* mask,
+                     float noise_prev, long B, long N, long F, void* noisy, float* ts_full, void* stream);
+/* The one-step denoise of the generated frames (causvid_vid_only.py:158-162): out = mask[f] ? noisy -
+ * ts_full[f] v : clean, in the latents' dtype; frames off the mask are copied bit for bit. */
+int owlk_causvid_x0(const void* noisy, const void* clean, int in_f32, const void* v, int v_f32,
+                    const float* ts_full, const void* mask, long B, long N, long F, void* out, void* stream);
+/* The generator loss (causvid_vid_only.py:268-306, the tail after the no-grad forwards) and its gradient to
+ * the student's velocity v, from which out = noisy - ts_full v was formed: v_t and norm_b as in owlk_dmd_loss
+ * with video = out, noisy = noisy2, ts = ts2; on the mask's frames g = nan_to_num(ts2 (v_t - v_critic) /
+ * norm_b) and r = out - orig; n = B N F; losses[0] = 0.5 sum g^2 / n, losses[1] = sum r^2 / n (frames off the
+ * mask count as zeros: an all-false mask gives {0, 0}); dv (the velocities' dtype) = -ts_full (g + 2
+ * reg_weight r) / n on the mask's frames and exact zeros elsewhere, the gradient of losses[0] + reg_weight
+ * losses[1].  ws: owlk_causvid_gen_loss_ws_bytes(B, N, F) bytes (fully written; no zeroing needed). */
+long owlk_causvid_gen_loss_ws_bytes(long B, long N, long F);
+int owlk_causvid_gen_loss(const void* out, const void* orig, const void* noisy2, int in_f32, const void* v_cond,
+                          const void* v_uncond, const void* v_critic, int v_f32, const float* ts2,
+                          const float* ts_full, const void* mask, long B, long N, long F, float cfg_scale,
+                          float reg_weight, float* losses, void* dv, void* ws, long ws_bytes, void* stream);
 /* out[n] += sum_r x[r, n] (bias gradients); x bf16 (x_f32 = 0) or fp32.  With ws (>=
  * owlk_colsum_ws_bytes(R, N) bytes, 16-B aligned) row splits store partial rows that one pass adds
  * in order (bitwise deterministic); without it the splits combine by fp32 atomics. */

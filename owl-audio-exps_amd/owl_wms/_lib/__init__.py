@@ -73,6 +73,10 @@ _SIGS = {
     "owlk_dmd_loss": [P, P, I, P, P, P, I, P, P, L, L, L, F, P, P, P, L, P],
     "owlk_critic_loss_ws_bytes": [L],
     "owlk_critic_loss": [P, I, P, P, I, P, L, L, L, F, P, P, P, L, P],
+    "owlk_causvid_mix": [P, P, I, P, P, F, L, L, L, P, P, P],
+    "owlk_causvid_x0": [P, P, I, P, I, P, P, L, L, L, P, P],
+    "owlk_causvid_gen_loss_ws_bytes": [L, L, L],
+    "owlk_causvid_gen_loss": [P, P, P, I, P, P, P, I, P, P, P, L, L, L, F, F, P, P, P, L, P],
     "owlk_gate_resid": [P, L, P, L, P, L, L, L, I, P, L, P],
     "owlk_colsum_ws_bytes": [L, L],
     "owlk_colsum": [P, I, L, L, L, P, P, L, P],
@@ -96,6 +100,7 @@ _RESTYPES = {n: ctypes.c_long for n in ("owlk_gemm_splitk_bytes", "owlk_gemm_ws_
                                          "owlk_qk_rope_bwd_ws_bytes", "owlk_attn_bwd_fused_ws_bytes",
                                         "owlk_attn_decode_bwd_ws_bytes",
                                         "owlk_dmd_loss_ws_bytes", "owlk_critic_loss_ws_bytes",
+                                        "owlk_causvid_gen_loss_ws_bytes",
                                         "owlk_colsum_ws_bytes", "owlk_ns_iterate_ws_bytes",
                                         "owlk_newton_schulz_ws_bytes", "owlk_grad_guard_ws_bytes")}
 

@@ -72,6 +72,10 @@ class TrainingConfig:
     update_ratio: int = 5  # critic updates per student update (every reference distillation config)
     rollout_steps: int = 1  # RolloutManager's defaults (sf_vid_only.py:113)
     min_rollout_frames: int = 8
+    regression_weight: float = 0.0  # CausVid (causvid_vid_only.py): weight of the regression to the clean frames
+    gen_mask_p: float = 0.25  # ... share of a window's frames the student generates (:106)
+    noise_prev: float = 0.2  # ... noise level of the others, its context (:105)
+    cfg_scale: float = 1.5  # ... the teacher's guidance in the DMD loss (:216)
     grad_guard: bool = False  # skip the optimizer step on a non-finite gradient; fused norm + clip
     grad_clip_norm: float = 10.0  # the non-Muon clip threshold (every reference trainer but mixed_av: 10)
     max_consecutive_skips: int = None  # with grad_guard: raise after more than this many skips in a row

@@ -911,6 +911,63 @@ def critic_loss(pred, z, video, mask, grad_scale=1.0):
     return loss, dpred
 
 
+def _frame_ts(name, what, ts, B, N):
+    if tuple(ts.shape) != (B, N):
+        raise RuntimeError(f"{name}: {what} has shape {tuple(ts.shape)}, [B, N] = {(B, N)} expected")
+    return ts.to(F32).contiguous()
+
+
+def causvid_mix(x, z, ts, mask=None, noise_prev=0.0):
+    """The CausVid noising (owlk_causvid_mix): x, z [B, N, ...] bf16 or fp32; ts [B, N]; mask [B, N] bool or
+    None -> (noisy in x's dtype = x (1 - t) + z t, ts_full fp32 [B, N] = t) with t = ts on the mask's frames
+    (every frame without a mask) and noise_prev elsewhere."""
+    B, N, F_ = _frames3("causvid_mix", x, {"z": z})
+    ts = _frame_ts("causvid_mix", "ts", ts, B, N)
+    m = None if mask is None else _frame_mask("causvid_mix", mask, B, N)
+    x, z = x.contiguous(), z.contiguous()
+    noisy, ts_full = torch.empty_like(x), torch.empty(B, N, device=x.device, dtype=F32)
+    call("owlk_causvid_mix", ptr(x), ptr(z), _in_dtype_flag(x, "x"), ptr(ts), ptr(m), float(noise_prev), B, N, F_,
+         ptr(noisy), ptr(ts_full), stream())
+    return noisy, ts_full
+
+
+def causvid_x0(noisy, clean, v, ts_full, mask):
+    """The CausVid one-step denoise (owlk_causvid_x0): noisy, clean [B, N, ...] bf16 or fp32, v bf16 (the
+    cores') or fp32, ts_full [B, N], mask [B, N] bool -> out in the latents' dtype = noisy - ts_full v on the
+    mask's frames, clean bit for bit elsewhere."""
+    B, N, F_ = _frames3("causvid_x0", noisy, {"clean": clean, "v": v}, {"v": v.dtype})
+    ts_full, m = _frame_ts("causvid_x0", "ts_full", ts_full, B, N), _frame_mask("causvid_x0", mask, B, N)
+    noisy, clean, v = noisy.contiguous(), clean.contiguous(), v.contiguous()
+    out = torch.empty_like(noisy)
+    call("owlk_causvid_x0", ptr(noisy), ptr(clean), _in_dtype_flag(noisy, "noisy"), ptr(v), _in_dtype_flag(v, "v"),
+         ptr(ts_full), ptr(m), B, N, F_, ptr(out), stream())
+    return out
+
+
+def causvid_gen_loss(out, orig, noisy2, v_cond, v_uncond, v_critic, ts2, ts_full, mask, cfg_scale, reg_weight):
+    """The CausVid generator loss tail (owlk_causvid_gen_loss): out, orig, noisy2 [B, N, ...] bf16 or fp32;
+    v_cond, v_uncond (None: no guidance), v_critic in one dtype, bf16 or fp32; ts2, ts_full [B, N]; mask [B, N]
+    bool -> (losses fp32 [2] = (dmd, regression), dv in the velocities' dtype: d (dmd + reg_weight regression) /
+    d v of the student's velocity v that made out = noisy - ts_full v, zero off the mask)."""
+    in_f32, v_f32 = _in_dtype_flag(out, "out"), _in_dtype_flag(v_cond, "v_cond")
+    B, N, F_ = _frames3("causvid_gen_loss", out, {"orig": orig, "noisy2": noisy2, "v_cond": v_cond,
+                                                  "v_uncond": v_uncond, "v_critic": v_critic},
+                        {"v_cond": v_cond.dtype, "v_uncond": v_cond.dtype, "v_critic": v_cond.dtype})
+    ts2 = _frame_ts("causvid_gen_loss", "ts2", ts2, B, N)
+    ts_full = _frame_ts("causvid_gen_loss", "ts_full", ts_full, B, N)
+    m = _frame_mask("causvid_gen_loss", mask, B, N)
+    out, orig, noisy2, v_cond, v_critic = (t.contiguous() for t in (out, orig, noisy2, v_cond, v_critic))
+    v_uncond = v_uncond.contiguous() if v_uncond is not None else None
+    nws = lib().owlk_causvid_gen_loss_ws_bytes(B, N, F_)
+    ws = torch.empty(max(nws, 4) // 4, device=out.device, dtype=F32)
+    losses = torch.empty(2, device=out.device, dtype=F32)
+    dv = torch.empty_like(v_cond)
+    call("owlk_causvid_gen_loss", ptr(out), ptr(orig), ptr(noisy2), in_f32, ptr(v_cond), ptr(v_uncond),
+         ptr(v_critic), v_f32, ptr(ts2), ptr(ts_full), ptr(m), B, N, F_, float(cfg_scale), float(reg_weight),
+         ptr(losses), ptr(dv), ptr(ws), nws, stream())
+    return losses, dv
+
+
 def colsum(x, out=None):
     """fp32 column sums of a 2-D row-major view (or a 3-D frame_rows view), added onto out
     (deterministic: row-split partials in a workspace, summed in order)."""

@@ -71,6 +71,10 @@ class GameRFTAudioCore(nn.Module):
         b, n, c, h, w = x.shape
         xv = x.permute(0, 1, 3, 4, 2).reshape(b, n * h * w, c)
         video, aud = self.forward_tokens(xv, audio, t, mouse, btn, has_controls, kv_cache)
+        if torch.is_grad_enabled() and video.requires_grad:
+            # as GameRFTCore.forward: the same rearrangement through autograd, for the distillation trainers
+            # that take a gradient through the velocity (trainers/causvid.py)
+            return video.view(b, n, h, w, c).permute(0, 1, 4, 2, 3).contiguous(), aud
         return K.unpatchify(video.reshape(-1, c).contiguous(), b, n, c, h, w), aud
 
 

@@ -14,7 +14,12 @@ def get_trainer_cls(trainer_id):
     if trainer_id == "sforce_vid":
         from .sf_trainer import SelfForceTrainer
         return SelfForceTrainer
-    raise NotImplementedError(f"trainer {trainer_id!r}: of the distillation trainers only the self-forcing one is "
-                              "built ('sforce_vid', trainers/sf_trainer.py over the rollout and the critic / DMD "
-                              "losses of trainers/self_forcing.py); 'causvid_vid' and 'ode_distill_vid' are not "
+    if trainer_id == "causvid":
+        from .causvid_trainer import CausVidTrainer
+        return CausVidTrainer
+    raise NotImplementedError(f"trainer {trainer_id!r}: of the distillation trainers the self-forcing one "
+                              "('sforce_vid', trainers/sf_trainer.py over the rollout and the critic / DMD "
+                              "losses of trainers/self_forcing.py) and CausVid ('causvid', trainers/"
+                              "causvid_trainer.py over trainers/causvid.py, for game_rft and game_rft_audio) are "
+                              "built; the ids 'causvid_vid' and 'ode_distill_vid' are not registered "
                               "(SURVEY.md §2.1)")

@@ -37,6 +37,12 @@ class RolloutNoise:
     def randn(self, shape, device, dtype):
         return torch.randn(*shape, device=device, dtype=dtype)
 
+    def rand(self, shape, device, dtype=torch.float32):
+        return torch.rand(*shape, device=device, dtype=dtype)
+
+    def randint(self, low, high, shape, device):
+        return torch.randint(low, high, tuple(shape), device=device, dtype=torch.long)
+
 
 class InjectedRolloutNoise:
     """Parity runs: replay pre-drawn tensors, one per draw, in call order (as models/flow.py's
@@ -57,9 +63,16 @@ class InjectedRolloutNoise:
     def randn(self, shape, device, dtype):
         return self._next(shape, device, dtype)
 
+    def rand(self, shape, device, dtype=torch.float32):
+        return self._next(shape, device, dtype)
 
-def _per_frame(t):
-    return t[:, :, None, None, None]
+    def randint(self, low, high, shape, device):
+        return self._next(shape, device, torch.long)
+
+
+def _per_frame(t, like=None):
+    """t [b, n] against a [b, n, c, h, w] video, or against ``like`` [b, n, ...] (the audio latents are [b, n, c])"""
+    return t[:, :, None, None, None] if like is None else t.reshape(t.shape + (1,) * (like.dim() - 2))
 
 
 def lerp_batched(x, z, t):
@@ -148,7 +161,7 @@ def _loss_draws(video, noise):
 
 def _critic_tail(pred, z, video, grad_mask):
     """the reference's tail (sf_vid_only.py:250-260) in torch, in the tensors' own dtype"""
-    m = _per_frame(grad_mask)
+    m = _per_frame(grad_mask, pred)
     return F.mse_loss(pred * m, (z - video) * m)
 
 
