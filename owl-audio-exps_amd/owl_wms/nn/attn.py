@@ -121,28 +121,22 @@ class Attn(nn.Module):
         D = d // H
         offset = kv_cache.get_offset(self.layer_idx) if kv_cache is not None else 0
         check_rope_rows(self.rope, offset, L)
-        if offset > 0 and getattr(kv_cache, "ring", False):
-            # RingKVCache (sampling/stream.py): the ring forms of the device-state decode kernels; the new
-            # rows wrap modulo the capacity, the addresses never move
-            if block_mask is not None or kv_cache.dev is None or not K.decode_dev_supported(D, L):
-                raise RuntimeError("a RingKVCache decodes one frame at a time on the device-state path "
-                                   f"(unmasked, head_dim 64 / 128, at most 64 rows; got head_dim {D}, {L} rows)")
+        ring = offset > 0 and getattr(kv_cache, "ring", False)
+        if ring and (block_mask is not None or kv_cache.dev is None or not K.decode_dev_supported(D, L)):
+            raise RuntimeError("a RingKVCache decodes one frame at a time on the device-state path "
+                               f"(unmasked, head_dim 64 / 128, at most 64 rows; got head_dim {D}, {L} rows)")
+        if ring or (block_mask is None and getattr(kv_cache, "dev", None) is not None and offset > 0 and
+                    K.decode_dev_supported(D, L)):
+            # decode with the cache position on the device (one captured graph for every frame).  A
+            # RingKVCache (sampling/stream.py) takes the kernels' ring forms: the new rows wrap modulo the
+            # capacity, the addresses never move
+            rope_kv, attend = (K.qk_rope_fwd_kv_ring, K.attn_decode_ring_fwd) if ring else \
+                (K.qk_rope_fwd_kv_dev, K.attn_decode_fwd)
             kb, vb = kv_cache.bufs[self.layer_idx]
             q = torch.empty(B, L, d, device=qkv.device, dtype=torch.bfloat16)
-            K.qk_rope_fwd_kv_ring(qkv, B, L, H, D, self.rope.cos, self.rope.sin, kv_cache.dev, q, kb, vb)
-            o, _ = K.attn_decode_ring_fwd(q, kb, vb, H, D, kv_cache.dev, L, self.local_offset if self.local else 0,
-                                          score_bound=K.qk_norm_bound(D))
-            if kv_cache.should_update:
-                kv_cache.commit_device(self.layer_idx, L)
-            return o
-        if block_mask is None and getattr(kv_cache, "dev", None) is not None and offset > 0 and \
-                K.decode_dev_supported(D, L):
-            # decode with the cache position on the device (one captured graph for every frame)
-            kb, vb = kv_cache.bufs[self.layer_idx]
-            q = torch.empty(B, L, d, device=qkv.device, dtype=torch.bfloat16)
-            K.qk_rope_fwd_kv_dev(qkv, B, L, H, D, self.rope.cos, self.rope.sin, kv_cache.dev, q, kb, vb)
-            o, _ = K.attn_decode_fwd(q, kb, vb, H, D, kv_cache.dev, L, self.local_offset if self.local else 0,
-                                     score_bound=K.qk_norm_bound(D))
+            rope_kv(qkv, B, L, H, D, self.rope.cos, self.rope.sin, kv_cache.dev, q, kb, vb)
+            o, _ = attend(q, kb, vb, H, D, kv_cache.dev, L, self.local_offset if self.local else 0,
+                          score_bound=K.qk_norm_bound(D))
             if kv_cache.should_update:
                 kv_cache.commit_device(self.layer_idx, L)
             return o

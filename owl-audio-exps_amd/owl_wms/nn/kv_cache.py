@@ -48,8 +48,15 @@ class SingleKVCache:
                     for dst, src in zip(new, (kb[0][:, s:s + n], kb[1][:, s:s + n])):
                         dst[:, :n].copy_(src)
                 self.bufs[i], self.start[i] = new, 0
+        self._create_device_state()
+
+    def _create_device_state(self):
         self.dev = torch.zeros(4, dtype=torch.int64, device=self.bufs[0][0].device)
         self.sync_device_state()
+
+    def _check_window(self, s, n):
+        """the live window [s, s + n) lies in the buffers"""
+        assert s + n <= self.bufs[0][0].shape[1]
 
     def sync_device_state(self):
         """host position -> the device vector (outside graph capture: an H2D copy)"""
@@ -58,7 +65,7 @@ class SingleKVCache:
         st = {(self.start[i], self.len[i], self.offsets[i]) for i in range(self.config.n_layers)}
         assert len(st) == 1, "device-state decode needs every layer at the same position"
         s, n, o = st.pop()
-        assert s + n <= self.bufs[0][0].shape[1]
+        self._check_window(s, n)
         self.dev.copy_(torch.tensor([s, n, o, 0], dtype=torch.int64))
 
     def commit_device(self, layer_ind, L):
@@ -150,11 +157,15 @@ class SingleKVCache:
         assert self.noise_caches == 0.0, "extend reads the cache as stored (noise_caches must be 0)"
         n, L = self.len[layer_ind], new_k.shape[1]
         self._reserve(layer_ind, n + L, new_k)
-        kb, vb = self.bufs[layer_ind]
-        s = self.start[layer_ind]
+        self._write_behind(layer_ind, n, new_k, new_v)
+        return self._views(layer_ind, n + L)
+
+    def _write_behind(self, i, n, new_k, new_v):
+        """new K/V into the rows behind the first n rows of layer i's window"""
+        kb, vb = self.bufs[i]
+        s, L = self.start[i], new_k.shape[1]
         kb[:, s + n:s + n + L].copy_(new_k)
         vb[:, s + n:s + n + L].copy_(new_v)
-        return self._views(layer_ind, n + L)
 
     def update(self, new_k, new_v, layer_ind):
         """kv_cache.py:47-58: the layer's cache becomes (new_k, new_v); a view returned by extend is
@@ -181,9 +192,13 @@ class SingleKVCache:
         for i in range(self.config.n_layers):
             amt_i = min(amt, self.len[i])
             if not front:
-                self.start[i] += amt_i
+                self.start[i] = self._advanced(self.start[i], amt_i)
             self.len[i] -= amt_i
         self.sync_device_state()
+
+    def _advanced(self, start, amt):
+        """the window's start after the oldest `amt` rows are dropped"""
+        return start + amt
 
     def length_at(self, idx):
         return self.len[idx]
@@ -257,17 +272,10 @@ class RingKVCache(SingleKVCache):
         final size, so this only creates the state vector."""
         assert capacity is None or capacity <= self.capacity, "a ring cache does not grow"
         assert all(b is not None for b in self.bufs), "enable_device_state after the context pass"
-        self.dev = torch.zeros(4, dtype=torch.int64, device=self.bufs[0][0].device)
-        self.sync_device_state()
+        self._create_device_state()
 
-    def sync_device_state(self):
-        if self.dev is None:
-            return
-        st = {(self.start[i], self.len[i], self.offsets[i]) for i in range(self.config.n_layers)}
-        assert len(st) == 1, "device-state decode needs every layer at the same position"
-        s, n, o = st.pop()
+    def _check_window(self, s, n):
         assert 0 <= s < self.capacity and 0 <= n <= self.capacity
-        self.dev.copy_(torch.tensor([s, n, o, 0], dtype=torch.int64))
 
     def commit_device(self, layer_ind, L):
         assert self.len[layer_ind] + L <= self.capacity, "ring capacity exceeded (evict before committing)"
@@ -278,19 +286,12 @@ class RingKVCache(SingleKVCache):
         raise RuntimeError("RingKVCache: the new rows may wrap, so there is no slot view; the ring rope kernel "
                            "(kernels.qk_rope_fwd_kv_ring) writes them")
 
-    def extended(self, layer_ind, L):
-        return self._views(layer_ind, self.len[layer_ind] + L)
-
-    def extend(self, layer_ind, new_k, new_v):
-        """new K/V written behind the window (wrapping); [cache | new] as gathered copies"""
-        assert self.noise_caches == 0.0, "extend reads the cache as stored (noise_caches must be 0)"
-        n, L = self.len[layer_ind], new_k.shape[1]
-        self._reserve(layer_ind, n + L, new_k)
-        kb, vb = self.bufs[layer_ind]
-        idx = self._rows(layer_ind, n, L)
+    def _write_behind(self, i, n, new_k, new_v):
+        """wrapping (extend then returns [cache | new] as gathered copies)"""
+        kb, vb = self.bufs[i]
+        idx = self._rows(i, n, new_k.shape[1])
         kb.index_copy_(1, idx, new_k)
         vb.index_copy_(1, idx, new_v)
-        return self._views(layer_ind, n + L)
 
     def update(self, new_k, new_v, layer_ind):
         """the layer's cache becomes (new_k, new_v), from row 0 (the context pass fills the ring)"""
@@ -304,14 +305,8 @@ class RingKVCache(SingleKVCache):
         vb[:, :L].copy_(new_v)
         self.start[layer_ind], self.len[layer_ind] = 0, L
 
-    def truncate(self, truncate_amt, front=False):
-        amt = truncate_amt * self.config.tokens_per_frame
-        for i in range(self.config.n_layers):
-            amt_i = min(amt, self.len[i])
-            if not front:
-                self.start[i] = (self.start[i] + amt_i) % self.capacity
-            self.len[i] -= amt_i
-        self.sync_device_state()
+    def _advanced(self, start, amt):
+        return (start + amt) % self.capacity
 
     def rebase(self, shift_tokens, rope=None):
         """Lower every live key's RoPE position by `shift_tokens` (whole frames): each layer's cached K is

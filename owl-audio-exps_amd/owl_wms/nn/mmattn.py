@@ -309,23 +309,38 @@ class MMDiTBlock(nn.Module):
         o, m = self.attn.out_projs[s], self.mlps[s]
         return o.weight, o.bias, m.fc1.weight, m.fc1.bias, m.fc2.weight, m.fc2.bias
 
-    def _forward_cached(self, x0, x1, cond0, cond1, block_mask, kv_cache):
-        """MMDiTBlock.forward (mmattn.py:98-114) with MMAttn's cache path (mmattn.py:46-72)."""
-        cfg, a = self.config, self.attn
-        d, H = cfg.d_model, cfg.n_heads
-        D = d // H
-        n0, n1 = cfg.sample_size ** 2, 1
-        B, T0, _ = x0.shape
-        nf = T0 // n0
-        T = nf * (n0 + n1)
-        ns = (n0, n1)
+    def _cached_dims(self, x0):
+        """(d, H, D, n0, n1, B, frames, joint rows per batch row) of a cached forward of x0 [B, frames n0, d]"""
+        cfg = self.config
+        d, H, n0, n1 = cfg.d_model, cfg.n_heads, cfg.sample_size ** 2, 1
+        nf = x0.shape[1] // n0
+        return d, H, d // H, n0, n1, x0.shape[0], nf, nf * (n0 + n1)
+
+    def _cached_head(self, x0, x1, cond0, cond1):
+        """What every cached forward opens with: per modality the bf16 rows xs, the modulation rows ms and
+        the qkv GEMM's output of the AdaLN-ed rows (AdaLN x 2, qkv GEMM x 2)."""
+        d, n0 = self.config.d_model, self.config.sample_size ** 2
         xs = (x0.reshape(-1, d).to(BF16).contiguous(), x1.reshape(-1, d).to(BF16).contiguous())
-        ms = (cond0.reshape(B * nf, 6 * d), cond1.reshape(B * nf, 6 * d))
+        ms = (cond0.reshape(-1, 6 * d), cond1.reshape(-1, 6 * d))
         qkv = []
-        for s in range(2):
-            h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
+        for s, n in enumerate((n0, 1)):
+            h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], n)
             wqkv, bqkv = self.qkv_params(s)
             qkv.append(K.gemm(h, bf16_weight(wqkv), bias=bqkv))
+        return xs, ms, qkv
+
+    def _cached_tail(self, os_, xs, ms, B):
+        """What every cached forward closes with: each modality's block_tail on its attention rows os_[s]
+        (4 launches each) -> the block's outputs [B, frames n0, d], [B, frames, d]."""
+        d, n0 = self.config.d_model, self.config.sample_size ** 2
+        outs = [block_tail(os_[s], xs[s], ms[s], n, self.tail_params(s), save=False)[0] for s, n in enumerate((n0, 1))]
+        return outs[0].view(B, -1, d), outs[1].view(B, -1, d)
+
+    def _forward_cached(self, x0, x1, cond0, cond1, block_mask, kv_cache):
+        """MMDiTBlock.forward (mmattn.py:98-114) with MMAttn's cache path (mmattn.py:46-72)."""
+        a = self.attn
+        d, H, D, n0, n1, B, nf, T = self._cached_dims(x0)
+        xs, ms, qkv = self._cached_head(x0, x1, cond0, cond1)
         qkvj = K.frame_interleave(qkv[0], qkv[1], n0, n1)
         del qkv
         li = a.layer_idx
@@ -344,9 +359,7 @@ class MMDiTBlock(nn.Module):
             kv_cache.update(k, v, li)
         mask = block_mask if block_mask is not None else K.FrameMask(1, None, False, 0, None)
         o, _ = K.attn_fwd(q, k, v, H, D, mask, score_bound=K.qk_norm_bound(D))
-        os_ = K.frame_split(o.view(B * T, d), n0, n1)
-        outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
-        return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
+        return self._cached_tail(K.frame_split(o.view(B * T, d), n0, n1), xs, ms, B)
 
     def _decode_ok(self, block_mask, kv_cache):
         """The fused decode path's cases (MMDIT.enable_decoding): head_dim 64, the causal frame mask, a
@@ -365,21 +378,9 @@ class MMDiTBlock(nn.Module):
         layer -- with the video / audio rows written apart, no frame_split); several frames keep the masked
         attn_fwd and are bit-identical to _forward_cached.  14 launches per block and decode step against
         18: AdaLN x 2, qkv GEMM x 2, rope, attention, block_tail x 2 (4 each)."""
-        cfg, a = self.config, self.attn
-        d, H = cfg.d_model, cfg.n_heads
-        D = d // H
-        n0, n1 = cfg.sample_size ** 2, 1
-        B, T0, _ = x0.shape
-        nf = T0 // n0
-        T = nf * (n0 + n1)
-        ns = (n0, n1)
-        xs = (x0.reshape(-1, d).to(BF16).contiguous(), x1.reshape(-1, d).to(BF16).contiguous())
-        ms = (cond0.reshape(B * nf, 6 * d), cond1.reshape(B * nf, 6 * d))
-        qkv = []
-        for s in range(2):
-            h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
-            wqkv, bqkv = self.qkv_params(s)
-            qkv.append(K.gemm(h, bf16_weight(wqkv), bias=bqkv))
+        a = self.attn
+        d, H, D, n0, n1, B, nf, T = self._cached_dims(x0)
+        xs, ms, qkv = self._cached_head(x0, x1, cond0, cond1)
         li = a.layer_idx
         offset = kv_cache.length_at(li)
         assert block_mask.q_offset == offset and block_mask.tpf == n0 + n1, "the frame mask describes this cache"
@@ -398,8 +399,7 @@ class MMDiTBlock(nn.Module):
         else:
             o, _ = K.attn_fwd(q, k, v, H, D, block_mask, score_bound=K.qk_norm_bound(D))
             os_ = K.frame_split(o.view(B * T, d), n0, n1)
-        outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
-        return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
+        return self._cached_tail(os_, xs, ms, B)
 
     def _forward_ring_decode(self, x0, x1, cond0, cond1, block_mask, kv_cache):
         """One new joint frame against a RingKVCache (sampling/stream.py AVFrameStream): _forward_decode's
@@ -410,27 +410,15 @@ class MMDiTBlock(nn.Module):
         The new rows are roped at the ABSOLUTE offset (the vector's third word), not at the cached length
         _forward_cached / _forward_decode use as mmattn.py:60-62 does: after an eviction the cached length
         points at positions live keys already hold."""
-        cfg, a = self.config, self.attn
-        d, H = cfg.d_model, cfg.n_heads
-        D = d // H
-        n0, n1 = cfg.sample_size ** 2, 1
-        B, T0, _ = x0.shape
-        nf = T0 // n0
+        a = self.attn
+        d, H, D, n0, n1, B, nf, T = self._cached_dims(x0)
         if nf != 1 or D != 64 or kv_cache.dev is None or kv_cache.noise_caches != 0.0 or \
                 not K.decode_joint_supported(D, n0, n1) or K.qk_norm_bound(D) <= 0.0:
             raise RuntimeError("a RingKVCache decodes one joint frame at a time on the device-state path (head_dim "
                                f"64, at most {K.JOINT_DECODE_ROWS} rows, noise_caches 0, enable_device_state() after "
                                f"the context pass; got {nf} frame(s) of {n0} + {n1} rows, head_dim {D}, noise_caches "
                                f"{kv_cache.noise_caches}, device state {'on' if kv_cache.dev is not None else 'off'})")
-        T = n0 + n1
-        ns = (n0, n1)
-        xs = (x0.reshape(-1, d).to(BF16).contiguous(), x1.reshape(-1, d).to(BF16).contiguous())
-        ms = (cond0.reshape(B * nf, 6 * d), cond1.reshape(B * nf, 6 * d))
-        qkv = []
-        for s in range(2):
-            h, _ = K.adaln_fwd(xs[s], ms[s][:, :d], ms[s][:, d:2 * d], ns[s])
-            wqkv, bqkv = self.qkv_params(s)
-            qkv.append(K.gemm(h, bf16_weight(wqkv), bias=bqkv))
+        xs, ms, qkv = self._cached_head(x0, x1, cond0, cond1)
         li = a.layer_idx
         kb, vb = kv_cache.bufs[li]
         q = torch.empty(B, T, d, device=x0.device, dtype=BF16)
@@ -441,8 +429,7 @@ class MMDiTBlock(nn.Module):
                                            score_bound=K.qk_norm_bound(D))[:2]
         if kv_cache.should_update:
             kv_cache.commit_device(li, T)
-        outs = [block_tail(os_[s], xs[s], ms[s], ns[s], self.tail_params(s), save=False)[0] for s in range(2)]
-        return outs[0].view(B, T0, d), outs[1].view(B, nf, d)
+        return self._cached_tail(os_, xs, ms, B)
 
 
 class MMDIT(nn.Module):

@@ -7,7 +7,7 @@ re-noise protocol as AVCachingSamplerV2.  Noise order: context zlerp, then per t
 import torch
 
 from ..nn.kv_cache import KVCache
-from .schedulers import get_deltas, get_sd3_euler
+from .schedulers import euler_dt, get_deltas, zlerp
 
 
 class AudioCachingSampler:
@@ -19,23 +19,16 @@ class AudioCachingSampler:
         self.custom_schedule = custom_schedule
         self.max_window = max_window
 
-    @staticmethod
-    def zlerp(x, alpha):
-        z = torch.randn_like(x)
-        return x * (1.0 - alpha) + z * alpha
-
     @torch.no_grad()
     def __call__(self, model, x, decode_fn=None, vae_scale=1.0, compile_on_decode=False):
         """model: an AudioRFT core; x [b, init_len, c] -> [b, init_len + num_tokens, c] (+ waveforms)."""
         batch_size, init_len, latent_channels = x.shape
-        if self.custom_schedule is None:
-            dt = get_sd3_euler(self.n_steps).to(device=x.device, dtype=x.dtype)
-        else:
-            dt = get_deltas(self.custom_schedule)
+        # a custom schedule's deltas stay Python floats here, as in the reference
+        dt = euler_dt(self.n_steps, None, x) if self.custom_schedule is None else get_deltas(self.custom_schedule)
         kv_cache = KVCache(model.config)
         kv_cache.reset(batch_size)
         latents = [x.clone()]
-        prev_x_noisy = self.zlerp(x, self.noise_prev)
+        prev_x_noisy = zlerp(x, self.noise_prev)
         prev_t = x.new_full((batch_size, x.size(1)), self.noise_prev)
         kv_cache.enable_cache_updates()
         model(prev_x_noisy, prev_t, doc_id=None, kv_cache=kv_cache)
@@ -50,7 +43,7 @@ class AudioCachingSampler:
                     curr_x = curr_x - dt[t_idx] * pred_v
                     curr_t = curr_t - dt[t_idx]
                 latents.append(curr_x.clone())
-                curr_x_noisy = self.zlerp(curr_x, self.noise_prev)
+                curr_x_noisy = zlerp(curr_x, self.noise_prev)
                 curr_t_noisy = torch.ones_like(curr_t) * self.noise_prev
                 kv_cache.enable_cache_updates()
                 model(curr_x_noisy, curr_t_noisy, kv_cache=kv_cache)

@@ -18,14 +18,20 @@ import torch
 from .. import kernels as K
 from ..nn.attn import check_rope_rows
 from ..nn.kv_cache import KVCache
-from .schedulers import get_deltas, get_sd3_euler
+from .schedulers import euler_dt, zlerp
+from .step_graph import StepGraph, _release_graph, capture
 
 
-def _release_graph(g):
-    """Destroy a step graph only after its queued replays have run: its exec (kernel arguments) and
-    its private memory pool are released here, so no replay of it may still be queued then."""
-    torch.cuda.current_stream().synchronize()
-    g.reset()
+def guided_velocity(model, kv_cache, cfg_scale, x, t, mouse, btn, null_mouse, null_btn):
+    """av_caching_v2.py:96-110: one prediction of the DiT core with optional CFG (cond | null controls as
+    one 2B batch, pred = uncond + cfg_scale (cond - uncond)); cfg_scale 1.0: the conditional pass alone."""
+    if cfg_scale == 1.0:
+        return model(x, t, mouse, btn, kv_cache=kv_cache)
+    B = x.shape[0]
+    pred = model(torch.cat([x, x]), torch.cat([t, t]), torch.cat([mouse, null_mouse]),
+                 torch.cat([btn, null_btn]), kv_cache=kv_cache)
+    pred_v, pred_u = pred[:B], pred[B:]
+    return pred_u + cfg_scale * (pred_v - pred_u)
 
 
 class AVCachingSamplerV2:
@@ -44,32 +50,21 @@ class AVCachingSamplerV2:
         # (False: the host-position path, one capture per frame with the cache length baked in)
         self.device_state = True
 
-    @staticmethod
-    def zlerp(x, alpha):
-        z = torch.randn_like(x)
-        return x * (1.0 - alpha) + z * alpha
-
     def _euler_step(self, model, kv_cache, x, t, mouse, btn, null_mouse, null_btn, dt):
-        """av_caching_v2.py:96-110: one Euler step with optional CFG (cond | uncond as one 2B batch)."""
-        if self.cfg_scale != 1.0:
-            B = x.shape[0]
-            pred = model(torch.cat([x, x]), torch.cat([t, t]), torch.cat([mouse, null_mouse]),
-                         torch.cat([btn, null_btn]), kv_cache=kv_cache)
-            pred_v, pred_u = pred[:B], pred[B:]
-            pred_v = pred_u + self.cfg_scale * (pred_v - pred_u)
-        else:
-            pred_v = model(x, t, mouse, btn, kv_cache=kv_cache)
+        """av_caching_v2.py:96-110: one Euler step with optional CFG (guided_velocity)."""
+        pred_v = guided_velocity(model, kv_cache, self.cfg_scale, x, t, mouse, btn, null_mouse, null_btn)
         return x - dt * pred_v, t - dt
 
-    def _euler_graphed(self, model, kv_cache, x, t, mouse, btn, null_mouse, null_btn, dt, warm=True):
-        """The frame's n_steps Euler steps replayed from one HIP graph.
+    def _graph_pool(self):
+        if self._pool is None:
+            self._pool = torch.cuda.graph_pool_handle()
+        return self._pool
 
-        The cache is read-only and fixed in length while a frame is denoised, so every step launches
-        the same kernels on the same buffers: one step is captured with x, t and dt in static device
-        buffers and replayed -- same kernels and arithmetic as the eager loop (the reference's
-        ``compile_on_decode`` switch).  With ``warm`` (the first frame) step 0
-        runs eagerly first: it creates the per-weight bf16 copies and workspaces outside the graph's
-        memory pool; later frames replay every step."""
+    def _euler_graphed(self, model, kv_cache, x, t, mouse, btn, null_mouse, null_btn, dt, warm=True):
+        """The frame's n_steps Euler steps replayed from one HIP graph, on the host-position path: the
+        cache length is baked into the launches, so every frame captures its own step (step_graph.capture)
+        with x, t and dt in static device buffers.  With ``warm`` (the first frame) step 0 runs eagerly
+        first (step_graph.py); later frames replay every step."""
         first = 0
         if warm:
             x, t = self._euler_step(model, kv_cache, x, t, mouse, btn, null_mouse, null_btn, dt[0])
@@ -77,17 +72,13 @@ class AVCachingSamplerV2:
             if self.n_steps == 1:
                 return x, t
         sx, st, sdt = x.clone(), t.clone(), dt[first].clone()
-        if self._pool is None:
-            self._pool = torch.cuda.graph_pool_handle()
-        g = torch.cuda.CUDAGraph()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, pool=self._pool, stream=side):
-                nx, nt = self._euler_step(model, kv_cache, sx, st, mouse, btn, null_mouse, null_btn, sdt)
-                sx.copy_(nx)
-                st.copy_(nt)
-        torch.cuda.current_stream().wait_stream(side)
+
+        def step():
+            nx, nt = self._euler_step(model, kv_cache, sx, st, mouse, btn, null_mouse, null_btn, sdt)
+            sx.copy_(nx)
+            st.copy_(nt)
+
+        g, _ = capture(step, self._graph_pool())
         for t_idx in range(first, self.n_steps):
             sdt.copy_(dt[t_idx])
             g.replay()
@@ -104,58 +95,38 @@ class AVCachingSamplerV2:
 
     def _euler_replay(self, model, kv_cache, x, t, mouse, btn, null_mouse, null_btn, dt):
         """compile_on_decode with the cache position on the device (SingleKVCache.enable_device_state):
-        ONE Euler step is captured on the first frame and replayed for every step of every frame
-        (its inputs are copied into the graph's static buffers first; the decode kernels read the
+        ONE Euler step is captured on the first frame (a StepGraph) and replayed for every step of every
+        frame (its inputs are copied into the graph's static buffers first; the decode kernels read the
         growing cache's position from the device).  The cache-update forward between frames stays
         eager: its launches overlap the replays still running on the GPU."""
-        st = self._step_graph
-        first = 0
-        if st is None:
+        sg, first = self._step_graph, 0
+        if sg is None:
             # first frame: step 0 eagerly (bf16 weight copies, workspaces outside the graph pool)
             x, t = self._euler_step(model, kv_cache, x, t, mouse, btn, null_mouse, null_btn, dt[0])
             if self.n_steps == 1:
                 return x, t
-            bufs = {"x": x.clone(), "t": t.clone(), "dt": dt[1].clone(), "mouse": mouse.clone(), "btn": btn.clone(),
-                    "nm": null_mouse.clone(), "nb": null_btn.clone()}
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                with torch.cuda.graph(g, pool=self._pool, stream=side):
-                    nx, nt = self._euler_step(model, kv_cache, bufs["x"], bufs["t"], bufs["mouse"], bufs["btn"],
-                                              bufs["nm"], bufs["nb"], bufs["dt"])
-                    bufs["x"].copy_(nx)
-                    bufs["t"].copy_(nt)
-            torch.cuda.current_stream().wait_stream(side)
-            self._step_graph = st = (g, bufs)
+            sg = self._step_graph = StepGraph(
+                lambda s, c, sdt: self._euler_step(model, kv_cache, s["x"], s["t"], c["mouse"], c["btn"], c["nm"],
+                                                   c["nb"], sdt),
+                {"x": x, "t": t}, {"mouse": mouse, "btn": btn, "nm": null_mouse, "nb": null_btn}, dt[1],
+                self._graph_pool())
             first = 1
         else:
-            g, bufs = st
             # the replayed step reads its positions from the device: check them here as the eager
             # step's Attn._attend does (the kernels would only poison the rows with NaN)
             rope = getattr(model.transformer, "rope", None)
             if rope is not None:
                 check_rope_rows(rope, kv_cache.get_offset(0), model.config.tokens_per_frame)
-            for k, v in (("x", x), ("t", t), ("mouse", mouse), ("btn", btn)):
-                bufs[k].copy_(v)
-        g, bufs = st
+            sg.load(x=x, t=t, mouse=mouse, btn=btn)  # the null controls are zeros: as captured
         for t_idx in range(first, self.n_steps):
-            bufs["dt"].copy_(dt[t_idx])
-            g.replay()
-        return bufs["x"].clone(), bufs["t"].clone()
+            sg.replay(dt[t_idx])
+        return sg.state()
 
     @torch.no_grad()
     def __call__(self, model, x, mouse, btn, compile_on_decode=False):
         """model: a GameRFTCore ([b,n,c,h,w] latents, kv_cache API); returns [b, init+new, c, h, w]."""
         batch_size, init_len = x.size(0), x.size(1)
-        if self.custom_schedule is None:
-            dt = get_sd3_euler(self.n_steps).to(device=x.device, dtype=x.dtype)
-        else:
-            # Python floats in the reference: fp32 device scalars (same opmath; a captured graph
-            # reads them from device memory)
-            dt = torch.tensor(get_deltas(list(self.custom_schedule)), device=x.device, dtype=torch.float32)
+        dt = euler_dt(self.n_steps, self.custom_schedule, x)
         cfg = self.cfg_scale != 1.0
         rep = (lambda *ts: [torch.cat([a, a]) for a in ts]) if cfg else (lambda *ts: list(ts))
         kv_cache = KVCache(model.config)
@@ -164,7 +135,7 @@ class AVCachingSamplerV2:
         latents = [x.clone()]
         prev_x = x
         prev_mouse, prev_btn = mouse[:, :init_len], btn[:, :init_len]
-        prev_x_noisy = self.zlerp(prev_x, self.noise_prev)
+        prev_x_noisy = zlerp(prev_x, self.noise_prev)
         prev_t = prev_x.new_full((batch_size, prev_x.size(1)), self.noise_prev)
         kv_cache.enable_cache_updates()
         model(*rep(prev_x_noisy, prev_t, prev_mouse, prev_btn), kv_cache=kv_cache)
@@ -198,7 +169,7 @@ class AVCachingSamplerV2:
                         curr_x, curr_t = self._euler_step(model, kv_cache, curr_x, curr_t, curr_mouse, curr_btn,
                                                           null_mouse, null_btn, dt[t_idx])
                 latents.append(curr_x.clone())
-                curr_x_noisy = self.zlerp(curr_x, self.noise_prev)
+                curr_x_noisy = zlerp(curr_x, self.noise_prev)
                 curr_t_noisy = torch.ones_like(curr_t) * self.noise_prev
                 kv_cache.enable_cache_updates()
                 model(*rep(curr_x_noisy, curr_t_noisy, curr_mouse, curr_btn), kv_cache=kv_cache)
@@ -208,7 +179,7 @@ class AVCachingSamplerV2:
         finally:
             model.transformer.disable_decoding()
             if self._step_graph is not None:
-                _release_graph(self._step_graph[0])
+                self._step_graph.release()
             self._step_graph = None
             if self._graph_prev is not None:
                 _release_graph(self._graph_prev[0])

@@ -31,13 +31,8 @@ import torch
 
 from ..nn.kv_cache import KVCache
 from ..utils import batch_permute_to_length
-from .av_caching_v2 import _release_graph
-from .schedulers import get_sd3_euler
-
-
-def zlerp(x, alpha):
-    z = torch.randn_like(x)
-    return x * (1. - alpha) + z * alpha
+from .schedulers import euler_dt, zlerp
+from .step_graph import _release_graph, capture
 
 
 class AVWindowSampler:
@@ -99,7 +94,7 @@ class AVWindowSampler:
         """model: a GameRFTAudioCore; video [b, n, c, h, w], audio [b, n, ca], mouse [b, n, 2], btn
         [b, n, n_buttons] -> latents [b, n + num_frames, ...] (the generated ones with only_return_generated)."""
         W = self.window_length
-        dt = get_sd3_euler(self.n_steps).to(device=video.device, dtype=video.dtype)
+        dt = euler_dt(self.n_steps, None, video)
         clean_v, clean_a = video.clone(), audio.clone()
         ext_mouse, ext_btn = batch_permute_to_length(mouse, btn, self.num_frames + W)
         hc = self._controls(video.shape[0], True, True, video.device)
@@ -168,7 +163,7 @@ class CausalAVWindowSampler(AVWindowSampler):
         W = self.window_length
         B = video.shape[0]
         cfg = self._cfg()
-        dt = get_sd3_euler(self.n_steps).to(device=video.device, dtype=video.dtype)
+        dt = euler_dt(self.n_steps, None, video)
         clean_v, clean_a = video.clone(), audio.clone()
         ext_mouse, ext_btn = batch_permute_to_length(mouse, btn, self.num_frames + W)
         hc = self._controls(B, cfg, self.conditioned, video.device)
@@ -183,13 +178,7 @@ class CausalAVWindowSampler(AVWindowSampler):
                 fixed = compile_on_decode and frame_idx > 0 and ins[0].shape[1] == W
                 if fixed and graph is None:
                     static = [t.clone() for t in ins]
-                    graph = torch.cuda.CUDAGraph()
-                    side = torch.cuda.Stream()
-                    side.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(side):
-                        with torch.cuda.graph(graph, stream=side):
-                            outs = self._denoise(model, cache, *static, dt, hc)
-                    torch.cuda.current_stream().wait_stream(side)
+                    graph, outs = capture(lambda: self._denoise(model, cache, *static, dt, hc))
                 if fixed and [t.shape for t in ins] == [t.shape for t in static]:
                     for dst, src in zip(static, ins):
                         dst.copy_(src)

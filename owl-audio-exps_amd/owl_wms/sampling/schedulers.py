@@ -24,3 +24,18 @@ def get_deltas(custom_schedule):
     if sched[-1] != 0.0:
         sched.append(0.0)
     return [abs(b - a) for a, b in zip(sched[:-1], sched[1:])]
+
+
+def euler_dt(n_steps, custom_schedule, like):
+    """The samplers' step sizes on like's device: the sd3 schedule in like's dtype, else a custom
+    schedule's deltas -- Python floats in the reference, here fp32 device scalars (same opmath; a
+    captured graph reads them from device memory)."""
+    if custom_schedule is None:
+        return get_sd3_euler(n_steps).to(device=like.device, dtype=like.dtype)
+    return torch.tensor(get_deltas(list(custom_schedule)), device=like.device, dtype=torch.float32)
+
+
+def zlerp(x, alpha):
+    """x re-noised to level alpha: one torch.randn_like draw"""
+    z = torch.randn_like(x)
+    return x * (1.0 - alpha) + z * alpha

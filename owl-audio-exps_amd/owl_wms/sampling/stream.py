@@ -29,16 +29,43 @@ from .. import kernels as K
 from ..nn.attn import check_rope_rows
 from ..nn.kv_cache import RingKVCache
 from ..utils import batch_permute_to_length
-from .av_caching_v2 import _release_graph
-from .schedulers import get_deltas, get_sd3_euler
+from .av_caching_v2 import guided_velocity
+from .schedulers import euler_dt, zlerp
+from .step_graph import StepGraph
 
 REBASE_ROPES = ("motion", "audio1d")  # angle tables linear in the frame index (prefix-stable)
 
 
 class _RingStream:
-    """What FrameStream and AVFrameStream share: the captured step's life cycle, zlerp and the RoPE rebase
-    of the ring cache.  Expects self.core, self.kv_cache, self.frames_generated, self.rebases and
-    self._step_graph = (graph, static buffers) or None."""
+    """FrameStream and AVFrameStream over a tuple of latents -- (x,) for video, (video, audio) for audio +
+    video: the context pass into a RingKVCache, one frame per step (rebase, draws, Euler steps eager or
+    replayed from one captured step, zlerp, the cache-updating forward, eviction) and the captured step's
+    life cycle.  A subclass supplies the core it accepts (its __init__), how one guided prediction is
+    formed (_guided) and how the core is called with the cache (_forward)."""
+
+    custom_schedule = None  # FrameStream's option
+    decoding = False  # transformer.enable_decoding() around a step (FrameStream)
+
+    def __init__(self, core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed):
+        name, cfg = type(self).__name__, core.config
+        if max_cached_frames < 1:
+            raise ValueError(f"{name}: max_cached_frames must be at least 1")
+        if max_cached_frames + 1 >= cfg.n_frames:
+            raise ValueError(f"{name}: max_cached_frames + 1 = {max_cached_frames + 1} must be below "
+                             f"config.n_frames = {cfg.n_frames}: the cached frames and the new one must fit the "
+                             "RoPE table with room to rebase into")
+        self.core = core
+        self.n_steps = n_steps
+        self.cfg_scale = cfg_scale
+        self.noise_prev = noise_prev
+        self.max_cached_frames = max_cached_frames
+        self.ring_frames = max_cached_frames + 1  # the ring's size in frames
+        self.graphed = graphed
+        self.frames_generated = 0
+        self.rebases = 0
+        self.kv_cache = None
+        self._step_graph = None
+        self._pool = None
 
     def __enter__(self):
         return self
@@ -50,14 +77,56 @@ class _RingStream:
     def close(self):
         """Release the captured step (after its queued replays have run)."""
         if self._step_graph is not None:
-            _release_graph(self._step_graph[0])
+            self._step_graph.release()
         self._step_graph = None
 
-    @staticmethod
-    def zlerp(x, alpha):
-        z = torch.randn_like(x)
-        return x * (1.0 - alpha) + z * alpha
+    def _cfg(self):
+        return self.cfg_scale != 1.0
 
+    def _rep(self, *ts):
+        return [torch.cat([a, a]) for a in ts] if self._cfg() else list(ts)
+
+    # ------------------------------------------------------------------ what a subclass supplies
+    def _forward(self, cache, xs, t, mouse, btn):
+        """The core on the latents xs at times t against `cache`, with CFG as one 2B batch [cond | uncond]
+        (the context pass, the cache-updating forward of a finished frame)."""
+        raise NotImplementedError
+
+    def _guided(self, xs, t, ctrl):
+        """One guided prediction per latent from the frame's controls `ctrl` (_controls)."""
+        raise NotImplementedError
+
+    def _controls(self, mouse_1, btn_1):
+        """The named per-frame inputs of _guided (the captured step's static input buffers)."""
+        return {"mouse": mouse_1, "btn": btn_1}
+
+    # ------------------------------------------------------------------ context
+    @torch.no_grad()
+    def _start(self, latents, mouse, btn):
+        """Cache the context frames: each latent zlerp-ed to noise_prev (in tuple order), one cache-updating
+        forward, then the position moves to the device."""
+        self.close()
+        core, cfg = self.core, self.core.config
+        B, init_len = latents[0].size(0), latents[0].size(1)
+        if not 1 <= init_len <= self.max_cached_frames:
+            raise ValueError(f"{type(self).__name__}.start: {init_len} context frames do not fit max_cached_frames = "
+                             f"{self.max_cached_frames}")
+        self._dt = euler_dt(self.n_steps, self.custom_schedule, latents[0])
+        cache = RingKVCache(cfg, self.ring_frames * cfg.tokens_per_frame, rope=core.transformer.rope)
+        cache.reset(2 * B if self._cfg() else B)
+        noisy = tuple(zlerp(x, self.noise_prev) for x in latents)
+        ts = latents[0].new_full((B, init_len), self.noise_prev)
+        cache.enable_cache_updates()
+        self._forward(cache, noisy, ts, mouse[:, :init_len], btn[:, :init_len])
+        cache.disable_cache_updates()
+        cache.enable_device_state()
+        self._like, self._t1 = tuple(x[:, :1] for x in latents), ts[:, :1]
+        self.kv_cache = cache
+        self.frames_generated = 0
+        self.rebases = 0
+        return self
+
+    # ------------------------------------------------------------------ one frame
     def _rebase_if_needed(self):
         """Before a frame whose rows would pass the RoPE table: re-rotate the cached K so that the
         oldest live key sits at position 0."""
@@ -75,154 +144,116 @@ class _RingStream:
         cache.rebase(off - len(cache), rope)
         self.rebases += 1
 
+    def _euler_step(self, xs, t, ctrl, dt):
+        """One Euler step of every latent from one guided prediction: x - dt * pred, t - dt."""
+        preds = self._guided(xs, t, ctrl)
+        return tuple(x - dt * p for x, p in zip(xs, preds)), t - dt
 
-class FrameStream(_RingStream):
-    def __init__(self, core, n_steps: int = 16, cfg_scale: float = 1.3, noise_prev: float = 0.2,
-                 max_cached_frames: int = 120, custom_schedule=None, graphed: bool = False) -> None:
-        cfg = core.config
-        if max_cached_frames < 1:
-            raise ValueError("FrameStream: max_cached_frames must be at least 1")
-        if max_cached_frames + 1 >= cfg.n_frames:
-            raise ValueError(f"FrameStream: max_cached_frames + 1 = {max_cached_frames + 1} must be below "
-                             f"config.n_frames = {cfg.n_frames}: the cached frames and the new one must fit the "
-                             "RoPE table with room to rebase into")
-        D = cfg.d_model // cfg.n_heads
-        if cfg.backbone != "dit" or not K.decode_dev_supported(D, cfg.tokens_per_frame):
-            raise ValueError("FrameStream: needs the DiT device-state decode path (head_dim 64 or 128, at most 64 "
-                             f"tokens per frame); got backbone {cfg.backbone!r}, head_dim {D}, "
-                             f"{cfg.tokens_per_frame} tokens per frame")
-        self.core = core
-        self.n_steps = n_steps
-        self.cfg_scale = cfg_scale
-        self.noise_prev = noise_prev
-        self.max_cached_frames = max_cached_frames
-        self.custom_schedule = custom_schedule
-        self.graphed = graphed
-        self.frames_generated = 0
-        self.rebases = 0
-        self.kv_cache = None
-        self._step_graph = None
-        self._pool = None
-
-    def _rep(self, *ts):
-        return [torch.cat([a, a]) for a in ts] if self.cfg_scale != 1.0 else list(ts)
-
-    @torch.no_grad()
-    def start(self, x, mouse, btn):
-        """Cache the context frames x [b, n, c, h, w] with their controls, as AVCachingSamplerV2 does
-        (zlerp at noise_prev; with CFG one 2B batch [cond | uncond])."""
-        self.close()
-        core, cfg = self.core, self.core.config
-        B, init_len = x.size(0), x.size(1)
-        if not 1 <= init_len <= self.max_cached_frames:
-            raise ValueError(f"FrameStream.start: {init_len} context frames do not fit max_cached_frames = "
-                             f"{self.max_cached_frames}")
-        if self.custom_schedule is None:
-            self._dt = get_sd3_euler(self.n_steps).to(device=x.device, dtype=x.dtype)
-        else:
-            self._dt = torch.tensor(get_deltas(list(self.custom_schedule)), device=x.device, dtype=torch.float32)
-        tpf = cfg.tokens_per_frame
-        cache = RingKVCache(cfg, (self.max_cached_frames + 1) * tpf, rope=core.transformer.rope)
-        cache.reset(2 * B if self.cfg_scale != 1.0 else B)
-        mouse, btn = mouse[:, :init_len], btn[:, :init_len]
-        x_noisy = self.zlerp(x, self.noise_prev)
-        self._t_prev = x.new_full((B, init_len), self.noise_prev)
-        cache.enable_cache_updates()
-        core(*self._rep(x_noisy, self._t_prev, mouse, btn), kv_cache=cache)
-        cache.disable_cache_updates()
-        cache.enable_device_state()
-        self._x1 = x[:, :1]
-        self.kv_cache = cache
-        self.frames_generated = 0
-        self.rebases = 0
-        return self
-
-    # ------------------------------------------------------------------ one frame
-    def _euler_step(self, x, t, mouse, btn, null_mouse, null_btn, dt):
-        """av_caching_v2.py:96-110: one Euler step with optional CFG (cond | uncond as one 2B batch)."""
-        core, cache = self.core, self.kv_cache
-        if self.cfg_scale != 1.0:
-            B = x.shape[0]
-            pred = core(torch.cat([x, x]), torch.cat([t, t]), torch.cat([mouse, null_mouse]),
-                        torch.cat([btn, null_btn]), kv_cache=cache)
-            pred_v, pred_u = pred[:B], pred[B:]
-            pred_v = pred_u + self.cfg_scale * (pred_v - pred_u)
-        else:
-            pred_v = core(x, t, mouse, btn, kv_cache=cache)
-        return x - dt * pred_v, t - dt
-
-    def _euler_replay(self, x, t, mouse, btn, null_mouse, null_btn):
-        """AVCachingSamplerV2._euler_replay: ONE Euler step captured on the first frame and replayed for
-        every step of every frame.  The ring's addresses are fixed and the kernels read the position
-        from the device, so wraps and rebases leave the graph valid."""
-        dt, st, first = self._dt, self._step_graph, 0
-        if st is None:
+    def _denoise(self, xs, t, ctrl):
+        """The frame's n_steps Euler steps.  graphed: ONE step captured on the first frame (a StepGraph) and
+        replayed for every step of every frame.  The ring's addresses are fixed and the kernels read the
+        position from the device, so wraps and rebases leave the graph valid."""
+        dt = self._dt
+        if not self.graphed:
+            for t_idx in range(self.n_steps):
+                xs, t = self._euler_step(xs, t, ctrl, dt[t_idx])
+            return xs, t
+        sg, first = self._step_graph, 0
+        names = [f"x{i}" for i in range(len(xs))]
+        if sg is None:
             # first frame: step 0 eagerly (bf16 weight copies, workspaces outside the graph pool)
-            x, t = self._euler_step(x, t, mouse, btn, null_mouse, null_btn, dt[0])
+            xs, t = self._euler_step(xs, t, ctrl, dt[0])
             if self.n_steps == 1:
-                return x, t
-            bufs = {"x": x.clone(), "t": t.clone(), "dt": dt[1].clone(), "mouse": mouse.clone(), "btn": btn.clone(),
-                    "nm": null_mouse.clone(), "nb": null_btn.clone()}
+                return xs, t
+
+            def step(s, c, sdt):
+                nxs, nt = self._euler_step(tuple(s[k] for k in names), s["t"], c, sdt)
+                return (*nxs, nt)
+
             if self._pool is None:
                 self._pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                with torch.cuda.graph(g, pool=self._pool, stream=side):
-                    nx, nt = self._euler_step(bufs["x"], bufs["t"], bufs["mouse"], bufs["btn"], bufs["nm"],
-                                              bufs["nb"], bufs["dt"])
-                    bufs["x"].copy_(nx)
-                    bufs["t"].copy_(nt)
-            torch.cuda.current_stream().wait_stream(side)
-            self._step_graph = st = (g, bufs)
+            sg = self._step_graph = StepGraph(step, {**dict(zip(names, xs)), "t": t}, ctrl, dt[1], self._pool)
             first = 1
         else:
-            g, bufs = st
             # the replayed step reads its positions from the device: check them here as the eager
-            # step's Attn._attend does (the kernels would only poison the rows with NaN)
+            # step's forward does (the kernels would only poison the rows with NaN)
             check_rope_rows(self.core.transformer.rope, self.kv_cache.get_offset(0),
                             self.core.config.tokens_per_frame)
-            for k, v in (("x", x), ("t", t), ("mouse", mouse), ("btn", btn)):
-                bufs[k].copy_(v)
-        g, bufs = st
+            # the frame's state and controls; any other input (null controls: zeros) stays as captured
+            sg.load(**dict(zip(names, xs)), t=t, mouse=ctrl["mouse"], btn=ctrl["btn"])
         for t_idx in range(first, self.n_steps):
-            bufs["dt"].copy_(dt[t_idx])
-            g.replay()
-        return bufs["x"].clone(), bufs["t"].clone()
+            sg.replay(dt[t_idx])
+        *xs, t = sg.state()
+        return tuple(xs), t
 
     @torch.no_grad()
-    def step(self, mouse_1, btn_1):
-        """One new frame from the controls mouse_1 [b, 1, 2], btn_1 [b, 1, n_buttons] -> [b, 1, c, h, w].
-        Denoises it over n_steps Euler steps, re-noises it (zlerp) and commits it to the cache, then
-        evicts the oldest frame once more than max_cached_frames are cached."""
+    def _step(self, mouse_1, btn_1):
+        """One new frame from the controls mouse_1 [b, 1, 2], btn_1 [b, 1, n_buttons] -> a tuple of latents
+        [b, 1, ...].  Draws one noise per latent (tuple order), denoises over n_steps Euler steps, re-noises
+        each latent (zlerp, tuple order) and commits the frame to the cache, then evicts the oldest frame
+        once more than max_cached_frames are cached."""
         if self.kv_cache is None:
-            raise RuntimeError("FrameStream.step before start(): cache the context frames first")
+            raise RuntimeError(f"{type(self).__name__}.step before start(): cache the context frames first")
         core, cache = self.core, self.kv_cache
         self._rebase_if_needed()
-        B = self._x1.size(0)
-        curr_x, curr_t = torch.randn_like(self._x1), self._t_prev.new_ones(B, 1)
-        null_mouse, null_btn = torch.zeros_like(mouse_1), torch.zeros_like(btn_1)
-        core.transformer.enable_decoding()
+        xs = tuple(torch.randn_like(x) for x in self._like)
+        t = torch.ones_like(self._t1)
+        ctrl = self._controls(mouse_1, btn_1)
+        if self.decoding:
+            core.transformer.enable_decoding()
         try:
-            if self.graphed:
-                curr_x, curr_t = self._euler_replay(curr_x, curr_t, mouse_1, btn_1, null_mouse, null_btn)
-            else:
-                for t_idx in range(self.n_steps):
-                    curr_x, curr_t = self._euler_step(curr_x, curr_t, mouse_1, btn_1, null_mouse, null_btn,
-                                                      self._dt[t_idx])
-            frame = curr_x.clone()
-            x_noisy = self.zlerp(curr_x, self.noise_prev)
-            t_noisy = torch.ones_like(curr_t) * self.noise_prev
+            xs, t = self._denoise(xs, t, ctrl)
+            frame = tuple(x.clone() for x in xs)
+            noisy = tuple(zlerp(x, self.noise_prev) for x in xs)
+            t_noisy = torch.ones_like(t) * self.noise_prev
             cache.enable_cache_updates()
-            core(*self._rep(x_noisy, t_noisy, mouse_1, btn_1), kv_cache=cache)
-            cache.disable_cache_updates()
+            self._forward(cache, noisy, t_noisy, mouse_1, btn_1)
         finally:
+            cache.disable_cache_updates()
             core.transformer.disable_decoding()
         if cache.n_frames() > self.max_cached_frames:
             cache.truncate(1, front=False)
         self.frames_generated += 1
         return frame
+
+
+class FrameStream(_RingStream):
+    """The video core (GameRFTCore on the DiT): ``pipe(controls) -> frame``.  CFG as AVCachingSamplerV2
+    forms it (guided_velocity: [cond | null controls]); both halves of the cache are filled from the
+    conditioned pass."""
+
+    decoding = True
+
+    def __init__(self, core, n_steps: int = 16, cfg_scale: float = 1.3, noise_prev: float = 0.2,
+                 max_cached_frames: int = 120, custom_schedule=None, graphed: bool = False) -> None:
+        super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed)
+        cfg = core.config
+        D = cfg.d_model // cfg.n_heads
+        if cfg.backbone != "dit" or not K.decode_dev_supported(D, cfg.tokens_per_frame):
+            raise ValueError("FrameStream: needs the DiT device-state decode path (head_dim 64 or 128, at most 64 "
+                             f"tokens per frame); got backbone {cfg.backbone!r}, head_dim {D}, "
+                             f"{cfg.tokens_per_frame} tokens per frame")
+        self.custom_schedule = custom_schedule
+
+    def _forward(self, cache, xs, t, mouse, btn):
+        return self.core(*self._rep(*xs, t, mouse, btn), kv_cache=cache)
+
+    def _controls(self, mouse_1, btn_1):
+        return {"mouse": mouse_1, "btn": btn_1, "nm": torch.zeros_like(mouse_1), "nb": torch.zeros_like(btn_1)}
+
+    def _guided(self, xs, t, ctrl):
+        return (guided_velocity(self.core, self.kv_cache, self.cfg_scale, xs[0], t, ctrl["mouse"], ctrl["btn"],
+                                ctrl["nm"], ctrl["nb"]),)
+
+    def start(self, x, mouse, btn):
+        """Cache the context frames x [b, n, c, h, w] with their controls, as AVCachingSamplerV2 does
+        (zlerp at noise_prev; with CFG one 2B batch [cond | uncond])."""
+        return self._start((x,), mouse, btn)
+
+    def step(self, mouse_1, btn_1):
+        """One new frame from the controls mouse_1 [b, 1, 2], btn_1 [b, 1, n_buttons] -> [b, 1, c, h, w]
+        (_RingStream._step)."""
+        return self._step(mouse_1, btn_1)[0]
 
 
 class StreamSampler:
@@ -282,144 +313,37 @@ class AVFrameStream(_RingStream):
         if cfg.backbone != "mmdit" or D != 64:
             raise ValueError("AVFrameStream: needs the MMDiT joint-frame decode path (backbone 'mmdit', head_dim 64); "
                              f"got backbone {cfg.backbone!r}, head_dim {D}")
-        if max_cached_frames < 1:
-            raise ValueError("AVFrameStream: max_cached_frames must be at least 1")
-        if max_cached_frames + 1 >= cfg.n_frames:
-            raise ValueError(f"AVFrameStream: max_cached_frames + 1 = {max_cached_frames + 1} must be below "
-                             f"config.n_frames = {cfg.n_frames}: the cached frames and the new one must fit the "
-                             "RoPE table with room to rebase into")
+        super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed)
         if ring_frames is not None and ring_frames < max_cached_frames + 1:
             raise ValueError(f"AVFrameStream: ring_frames = {ring_frames} cannot hold max_cached_frames + 1 = "
                              f"{max_cached_frames + 1} frames")
-        self.core = core
-        self.n_steps = n_steps
-        self.cfg_scale = cfg_scale
-        self.noise_prev = noise_prev
-        self.max_cached_frames = max_cached_frames
-        self.ring_frames = ring_frames if ring_frames is not None else max_cached_frames + 1
-        self.graphed = graphed
-        self.frames_generated = 0
-        self.rebases = 0
-        self.kv_cache = None
-        self._step_graph = None
-        self._pool = None
+        if ring_frames is not None:
+            self.ring_frames = ring_frames
 
-    def _cfg(self):
-        return self.cfg_scale != 1.0
+    def _forward(self, cache, xs, t, mouse, btn):
+        return self.core(*self._rep(*xs, t, mouse, btn), has_controls=self._hc, kv_cache=cache)
 
-    def _rep(self, *ts):
-        return [torch.cat([a, a]) for a in ts] if self._cfg() else list(ts)
+    def _guided(self, xs, t, ctrl):
+        pv, pa = self._forward(self.kv_cache, xs, t, ctrl["mouse"], ctrl["btn"])
+        if self._cfg():
+            B = xs[0].shape[0]
+            pv = pv[B:] + self.cfg_scale * (pv[:B] - pv[B:])
+            pa = pa[B:] + self.cfg_scale * (pa[:B] - pa[B:])
+        return pv, pa
 
-    @torch.no_grad()
     def start(self, video, audio, mouse, btn):
         """Cache the context frames video [b, n, c, h, w] / audio [b, n, ca] with their controls: each
         zlerp-ed to noise_prev, one cache-updating forward (with CFG one 2B batch [cond | uncond])."""
-        self.close()
-        core, cfg = self.core, self.core.config
-        B, init_len = video.size(0), video.size(1)
-        if not 1 <= init_len <= self.max_cached_frames:
-            raise ValueError(f"AVFrameStream.start: {init_len} context frames do not fit max_cached_frames = "
-                             f"{self.max_cached_frames}")
-        self._dt = get_sd3_euler(self.n_steps).to(device=video.device, dtype=video.dtype)
-        cache = RingKVCache(cfg, self.ring_frames * cfg.tokens_per_frame, rope=core.transformer.rope)
-        cache.reset(2 * B if self._cfg() else B)
-        mouse, btn = mouse[:, :init_len], btn[:, :init_len]
-        v_noisy = self.zlerp(video, self.noise_prev)
-        a_noisy = self.zlerp(audio, self.noise_prev)
-        ts = video.new_full((B, init_len), self.noise_prev)
+        B = video.size(0)
         self._hc = torch.ones(2 * B if self._cfg() else B, dtype=torch.bool, device=video.device)
         if self._cfg():
             self._hc[B:] = False
-        cache.enable_cache_updates()
-        core(*self._rep(v_noisy, a_noisy, ts, mouse, btn), has_controls=self._hc, kv_cache=cache)
-        cache.disable_cache_updates()
-        cache.enable_device_state()
-        self._v1, self._a1, self._t1 = video[:, :1], audio[:, :1], ts[:, :1]
-        self.kv_cache = cache
-        self.frames_generated = 0
-        self.rebases = 0
-        return self
+        return self._start((video, audio), mouse, btn)
 
-    # ------------------------------------------------------------------ one frame
-    def _euler_step(self, xv, xa, t, mouse, btn, dt):
-        """One Euler step of both modalities from one forward (FrameStream._euler_step's arithmetic)."""
-        pv, pa = self.core(*self._rep(xv, xa, t, mouse, btn), has_controls=self._hc, kv_cache=self.kv_cache)
-        if self._cfg():
-            B = xv.shape[0]
-            pv = pv[B:] + self.cfg_scale * (pv[:B] - pv[B:])
-            pa = pa[B:] + self.cfg_scale * (pa[:B] - pa[B:])
-        return xv - dt * pv, xa - dt * pa, t - dt
-
-    def _euler_replay(self, xv, xa, t, mouse, btn):
-        """FrameStream._euler_replay for two modalities: step 0 of the first frame eagerly, then ONE
-        captured Euler step replayed for every step of every frame (the ring's addresses are fixed and
-        the kernels read the position from the device)."""
-        dt, st, first = self._dt, self._step_graph, 0
-        if st is None:
-            xv, xa, t = self._euler_step(xv, xa, t, mouse, btn, dt[0])
-            if self.n_steps == 1:
-                return xv, xa, t
-            bufs = {"xv": xv.clone(), "xa": xa.clone(), "t": t.clone(), "dt": dt[1].clone(), "mouse": mouse.clone(),
-                    "btn": btn.clone()}
-            if self._pool is None:
-                self._pool = torch.cuda.graph_pool_handle()
-            g = torch.cuda.CUDAGraph()
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                with torch.cuda.graph(g, pool=self._pool, stream=side):
-                    nv, na, nt = self._euler_step(bufs["xv"], bufs["xa"], bufs["t"], bufs["mouse"], bufs["btn"],
-                                                  bufs["dt"])
-                    bufs["xv"].copy_(nv)
-                    bufs["xa"].copy_(na)
-                    bufs["t"].copy_(nt)
-            torch.cuda.current_stream().wait_stream(side)
-            self._step_graph = st = (g, bufs)
-            first = 1
-        else:
-            g, bufs = st
-            # the replayed step reads its positions from the device: check them here as the eager
-            # step's MMDIT.forward does (the kernels would only poison the rows with NaN)
-            check_rope_rows(self.core.transformer.rope, self.kv_cache.get_offset(0),
-                            self.core.config.tokens_per_frame)
-            for k, v in (("xv", xv), ("xa", xa), ("t", t), ("mouse", mouse), ("btn", btn)):
-                bufs[k].copy_(v)
-        g, bufs = st
-        for t_idx in range(first, self.n_steps):
-            bufs["dt"].copy_(dt[t_idx])
-            g.replay()
-        return bufs["xv"].clone(), bufs["xa"].clone(), bufs["t"].clone()
-
-    @torch.no_grad()
     def step(self, mouse_1, btn_1):
         """One new frame from the controls mouse_1 [b, 1, 2], btn_1 [b, 1, n_buttons] -> (video
-        [b, 1, c, h, w], audio [b, 1, ca]).  Denoises it over n_steps Euler steps, re-noises both
-        modalities (zlerp) and commits the frame to the cache, then evicts the oldest frame once more
-        than max_cached_frames are cached."""
-        if self.kv_cache is None:
-            raise RuntimeError("AVFrameStream.step before start(): cache the context frames first")
-        core, cache = self.core, self.kv_cache
-        self._rebase_if_needed()
-        xv, xa = torch.randn_like(self._v1), torch.randn_like(self._a1)
-        t = torch.ones_like(self._t1)
-        if self.graphed:
-            xv, xa, t = self._euler_replay(xv, xa, t, mouse_1, btn_1)
-        else:
-            for t_idx in range(self.n_steps):
-                xv, xa, t = self._euler_step(xv, xa, t, mouse_1, btn_1, self._dt[t_idx])
-        video, audio = xv.clone(), xa.clone()
-        v_noisy = self.zlerp(xv, self.noise_prev)
-        a_noisy = self.zlerp(xa, self.noise_prev)
-        t_noisy = torch.ones_like(t) * self.noise_prev
-        cache.enable_cache_updates()
-        try:
-            core(*self._rep(v_noisy, a_noisy, t_noisy, mouse_1, btn_1), has_controls=self._hc, kv_cache=cache)
-        finally:
-            cache.disable_cache_updates()
-        if cache.n_frames() > self.max_cached_frames:
-            cache.truncate(1, front=False)
-        self.frames_generated += 1
-        return video, audio
+        [b, 1, c, h, w], audio [b, 1, ca]) (_RingStream._step)."""
+        return self._step(mouse_1, btn_1)
 
 
 class AVStreamSampler:

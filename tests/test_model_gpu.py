@@ -525,13 +525,19 @@ def test_trainer_reads_packed_table(tmp_path):
     assert all(torch.isfinite(torch.tensor(h["diffusion_loss"])) for h in tr.history)
 
 
-@pytest.mark.parametrize("n_steps,cfg,custom,d_model", [(4, 1.3, None, 128), (3, 1.0, None, 128),
-                                                       (3, 1.3, [1.0, 0.7, 0.3], 128), (3, 1.3, None, 256)])
-def test_graphed_decode_equals_eager(n_steps, cfg, custom, d_model):
+@pytest.mark.parametrize("n_steps,cfg,custom,d_model,device_state", [
+    pytest.param(4, 1.3, None, 128, True, id="4-1.3-None-128"),
+    pytest.param(3, 1.0, None, 128, True, id="3-1.0-None-128"),
+    pytest.param(3, 1.3, [1.0, 0.7, 0.3], 128, True, id="3-1.3-custom2-128"),
+    pytest.param(3, 1.3, None, 256, True, id="3-1.3-None-256"),
+    pytest.param(3, 1.3, None, 128, False, id="3-1.3-None-128-host")])
+def test_graphed_decode_equals_eager(n_steps, cfg, custom, d_model, device_state):
     """compile_on_decode: the per-frame Euler steps replayed from a HIP graph give the same sampled
     latents as the eager loop, bit for bit (same kernels, same buffers' contents, same order);
     also with a custom schedule (its deltas live in device memory the graph reads) and at head_dim
-    128 (d_model 256: dit_v4_5B's decode shape)."""
+    128 (d_model 256: dit_v4_5B's decode shape).  The "host" case sets the sampler's device_state
+    False: the host-position path, one capture per frame (AVCachingSamplerV2._euler_graphed), a warm
+    first frame and all-replay later frames."""
     from owl_wms.sampling import get_sampler_cls
     m = _model(d_model).eval()
     g = torch.Generator().manual_seed(5)
@@ -543,6 +549,7 @@ def test_graphed_decode_equals_eager(n_steps, cfg, custom, d_model):
         torch.manual_seed(123)
         s = get_sampler_cls("av_caching")(n_steps=n_steps, cfg_scale=cfg, num_frames=4, noise_prev=0.2,
                                           custom_schedule=custom)
+        s.device_state = device_state
         outs.append(s(m.core, x, mouse, btn, compile_on_decode=graphed))
     assert outs[0].shape == (2, 8, 32, 8, 8)
     assert torch.equal(outs[0], outs[1])
