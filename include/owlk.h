@@ -276,6 +276,20 @@ int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb, const voi
                                     float* lse, long B, int H, int n0, int n1, int head_dim, float scale,
                                     float score_bound, const long* state, long window_tokens, long cap,
                                     void* stream);
+/* Wide ring decode for streaming the dit-backbone audio + video core (the reference's
+ * inference/causvid_pipeline.py on configs/causvid.yml: a 65-row joint frame [64 video | 1 audio] through the
+ * plain DiT, attn.py:86-107 cache branch): owlk_attn_decode_ring_fwd's arguments with one frame of
+ * 0 < Lq <= 80 query rows per (batch, head), head_dim 64, bounded softmax only.  Keys are the logical
+ * [cache | Lnew new rows] of the ring (total = cached + Lnew), or the last window_tokens of them; logical
+ * key i lives at physical row (start + first + i) mod cap.  One output o [B, Lq, H D] with its own row and
+ * batch stride (the DiT's out-projection operand), lse [B, H, Lq] base 2 or null.  The joint ring kernel's
+ * body and tile decomposition: o and lse equal owlk_attn_decode_joint_ring_fwd's o0 | o1 and lse on the
+ * same buffers and state bit for bit.  Contract: 0 <= start < cap, cached >= 0, cached + Lnew <= cap;
+ * outside it every o row and lse entry NaN, nothing read. */
+int owlk_attn_decode_wide_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                   const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
+                                   long B, int H, long Lq, int head_dim, float scale, float score_bound,
+                                   const long* state, long Lnew, long window_tokens, long cap, void* stream);
 /* delta[b, h, t] = sum_d dO * O (fp32), the backward's row constant */
 int owlk_attn_delta(const void* o, const void* dout, long ld, long B, long L, int H, int D, float* delta,
                     void* stream);

@@ -1003,17 +1003,36 @@ struct JointRingP : JointP {
   const long* state;  // {start, cached tokens, rope offset}
   long wtok, cap;
 };
-template <bool RING>
-using JointArg = std::conditional_t<RING, JointRingP, JointP>;
+// WIDE (owlk_attn_decode_wide_ring_fwd, the DiT's 65-row audio + video frame on the attn.py:86-107 cache
+// branch): the ring form with ONE output o0 [B, Lq, H D] of row stride ldo0 and batch stride sob (the DiT's
+// out-projection operand; o1 / n0 / n1 unused) and Lnew new rows behind the cache, total = cached + Lnew.
+// Only joint_out_row and the total differ, so o and lse equal the joint ring kernel's o0 | o1 and lse.
+struct WideRingP : JointRingP {
+  long sob, Lnew;
+};
+template <bool RING, bool WIDE>
+using JointArg = std::conditional_t<WIDE, WideRingP, std::conditional_t<RING, JointRingP, JointP>>;
 
-template <bool RING = false>
-__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING> p) {
+// where query row q of batch b goes: the video / audio split of the joint frame, or the one wide output
+template <bool WIDE, class P>
+__device__ __forceinline__ bf16* joint_out_row(const P& p, long b, int q) {
+  if constexpr (WIDE)
+    return p.o0 + b * p.sob + (long)q * p.ldo0;
+  else
+    return q < p.n0 ? p.o0 + (b * p.n0 + q) * p.ldo0 : p.o1 + (b * p.n1 + (q - p.n0)) * p.ldo1;
+}
+
+template <bool RING = false, bool WIDE = false>
+__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING, WIDE> p) {
+  static_assert(RING || !WIDE, "the wide output comes in the ring form only");
   using C = DecCfg<64>;
   constexpr int D = 64, KTD = C::KTD, NQT = JointCfg::NQT, QR = JointCfg::QR;
   long org = 0, cap = 0;
   if constexpr (RING) {
     cap = p.cap;
-    const long start = p.state[0], cached = p.state[1], total = cached + p.Lq, wtok = p.wtok;
+    long lnew = p.Lq;
+    if constexpr (WIDE) lnew = p.Lnew;
+    const long start = p.state[0], cached = p.state[1], total = cached + lnew, wtok = p.wtok;
     if (start < 0 || start >= cap || cached < 0 || total > cap) {
       const long b = blockIdx.z;
       const int head = blockIdx.y;
@@ -1023,8 +1042,7 @@ __global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING> p) 
       for (int item = threadIdx.x; item < 4 * QR; item += 256) {
         const int q = item >> 2, d0 = 16 * (item & 3);
         if (q >= p.Lq) continue;
-        bf16* O =
-            (q < p.n0 ? p.o0 + (b * p.n0 + q) * p.ldo0 : p.o1 + (b * p.n1 + (q - p.n0)) * p.ldo1) + head * D + d0;
+        bf16* O = joint_out_row<WIDE>(p, b, q) + head * D + d0;
         *(bf16x8*)O = nan8;
         *(bf16x8*)(O + 8) = nan8;
         if ((item & 3) == 0 && p.lse) p.lse[(b * p.H + head) * p.Lq + q] = NAN;
@@ -1181,7 +1199,7 @@ __global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING> p) 
 #pragma unroll
     for (int ww = 0; ww < 4; ++ww) l += lsum[ww * QR + q];
     const float inv = l > 0.f ? 1.f / l : 0.f;
-    bf16* O = (q < p.n0 ? p.o0 + (b * p.n0 + q) * p.ldo0 : p.o1 + (b * p.n1 + (q - p.n0)) * p.ldo1) + head * D + d0;
+    bf16* O = joint_out_row<WIDE>(p, b, q) + head * D + d0;
 #pragma unroll
     for (int h8 = 0; h8 < 2; ++h8) {
       float v[8];
@@ -1439,4 +1457,41 @@ extern "C" int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb
   hipLaunchKernelGGL(attn_decode_joint_k<true>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
                      p);
   return owlk::check_launch("attn_decode_joint_ring_fwd");
+}
+
+// The DiT's own form of the five-tile ring decode, for streaming the dit-backbone audio + video core (the
+// reference's inference/causvid_pipeline.py: pipe(new_mouse, new_btn) -> frame, a 65-row joint frame through
+// the attn.py:86-107 cache branch): owlk_attn_decode_ring_fwd's arguments at 0 < Lq <= 80 query rows,
+// head_dim 64.  attn_decode_joint_k's ring body with one output o [B, Lq, H D] (row stride ldo, batch stride
+// sob): the same bits as owlk_attn_decode_joint_ring_fwd's o0 | o1 and lse on the same buffers and state.
+// Contract: 0 <= start < cap, cached >= 0, cached + Lnew <= cap; outside it NaN o rows and lse, nothing read.
+extern "C" int owlk_attn_decode_wide_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                              long skb, const void* vbuf, long ldv, long svb, void* o, long ldo,
+                                              long sob, float* lse, long B, int H, long Lq, int head_dim, float scale,
+                                              float score_bound, const long* state, long Lnew, long window_tokens,
+                                              long cap, void* stream) {
+  OWLK_REQUIRE(head_dim == 64, "attn_decode_wide_ring_fwd: head_dim %d not built (64)", head_dim);
+  OWLK_REQUIRE(B > 0 && H > 0 && B <= 65535 && H <= 65535 && Lnew > 0 && state && window_tokens >= 0,
+               "attn_decode_wide_ring_fwd: bad sizes");
+  OWLK_REQUIRE(Lq > 0 && Lq <= JointCfg::QR, "attn_decode_wide_ring_fwd: one frame of at most %d rows (got %ld)",
+               JointCfg::QR, Lq);
+  OWLK_REQUIRE(cap >= Lnew, "attn_decode_wide_ring_fwd: cache capacity %ld rows", cap);
+  OWLK_REQUIRE(score_bound > 0.f && score_bound * scale < 40.f, "attn_decode_wide_ring_fwd: needs a score bound");
+  OWLK_REQUIRE(((uintptr_t)q | (uintptr_t)kbuf | (uintptr_t)vbuf | (uintptr_t)o) % 16 == 0 && ldq % 8 == 0 &&
+                   ldk % 8 == 0 && ldv % 8 == 0 && ldo % 8 == 0 && sqb % 8 == 0 && skb % 8 == 0 && svb % 8 == 0 &&
+                   sob % 8 == 0,
+               "attn_decode_wide_ring_fwd: q/k/v/o rows must be 16-byte aligned");
+  const long hd = (long)H * head_dim;
+  OWLK_REQUIRE(ldq >= hd && ldk >= hd && ldv >= hd && ldo >= hd,
+               "attn_decode_wide_ring_fwd: a row stride is shorter than its H * head_dim columns");
+  WideRingP p;
+  p.state = state; p.wtok = window_tokens; p.cap = cap; p.sob = sob; p.Lnew = Lnew;
+  p.q = (const bf16*)q; p.k = (const bf16*)kbuf; p.v = (const bf16*)vbuf;
+  p.o0 = (bf16*)o; p.o1 = nullptr; p.lse = lse;
+  p.ldq = ldq; p.sqb = sqb; p.ldk = ldk; p.skb = skb; p.ldv = ldv; p.svb = svb; p.ldo0 = ldo; p.ldo1 = 0;
+  p.Lq = Lq; p.Lkv = 0; p.n0 = (int)Lq; p.n1 = 0; p.H = H;  // Lkv from the device state
+  p.scale_log2 = scale * LOG2E;
+  hipLaunchKernelGGL((attn_decode_joint_k<true, true>), dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0,
+                     (hipStream_t)stream, p);
+  return owlk::check_launch("attn_decode_wide_ring_fwd");
 }

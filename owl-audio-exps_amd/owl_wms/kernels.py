@@ -491,6 +491,38 @@ def attn_decode_joint_ring_fwd(q, kbuf, vbuf, H, D, n0, n1, state, window_tokens
     return o0, o1, lse
 
 
+WIDE_DECODE_ROWS = 80  # owlk_attn_decode_wide_ring_fwd: query rows of one frame (five 16-row tiles)
+
+
+def decode_wide_supported(D, L):
+    """owlk_attn_decode_wide_ring_fwd's shapes past owlk_attn_decode_ring_fwd's: head_dim 64, one frame of
+    65 to 80 query rows (the dit backbone's audio + video frame)."""
+    return D == 64 and 64 < L <= WIDE_DECODE_ROWS
+
+
+def attn_decode_wide_ring_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0, scale=None, score_bound=0.0,
+                              o=None):
+    """attn_decode_ring_fwd for one frame of up to 80 query rows (head_dim 64): q [B, Lq, H D] against the
+    logical keys [cache | Lnew new rows] of the ring (or their last window_tokens), logical key i at physical
+    row (start + first + i) mod cap -> o [B, Lq, H D] (`o`: a destination view with any row / batch
+    stride), lse [B, H, Lq] (base 2).  The bits of attn_decode_joint_ring_fwd's o0 | o1 and lse."""
+    _v3(q, "q")
+    B, Lq = q.shape[0], q.shape[1]
+    assert D == 64 and 0 < Lq <= WIDE_DECODE_ROWS, \
+        f"attn_decode_wide_ring_fwd: head_dim {D} / {Lq} query rows not supported"
+    assert q.shape[2] >= H * D
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    if o is None:
+        o = torch.empty(B, Lq, H * D, device=q.device, dtype=BF16)
+    assert o.shape == (B, Lq, H * D) and o.stride(2) == 1 and o.dtype == BF16 and o.device == q.device, "o"
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32)
+    call("owlk_attn_decode_wide_ring_fwd", ptr(q), q.stride(1), q.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), ptr(o), o.stride(1), o.stride(0), ptr(lse), B, H,
+         Lq, D, float(scale if scale is not None else D ** -0.5), float(score_bound), ptr(state), int(Lnew),
+         int(window_tokens), kbuf.shape[1], stream())
+    return o, lse
+
+
 def qk_rope_bwd(dqk, qkv, rstd, H, D, cos, sin, dqkv, tab_off=0, tpos_div=0, dbias=None):
     """-> dqkv[:, :2HD]; with dbias (fp32 [2HD]) also dbias += column sums of those outputs (the q / k
     part of the qkv bias gradient), fused into the same pass where the shape allows."""

@@ -122,16 +122,20 @@ class Attn(nn.Module):
         offset = kv_cache.get_offset(self.layer_idx) if kv_cache is not None else 0
         check_rope_rows(self.rope, offset, L)
         ring = offset > 0 and getattr(kv_cache, "ring", False)
-        if ring and (block_mask is not None or kv_cache.dev is None or not K.decode_dev_supported(D, L)):
+        wide = ring and K.decode_wide_supported(D, L)
+        if ring and (block_mask is not None or kv_cache.dev is None or
+                     not (wide or K.decode_dev_supported(D, L))):
             raise RuntimeError("a RingKVCache decodes one frame at a time on the device-state path "
-                               f"(unmasked, head_dim 64 / 128, at most 64 rows; got head_dim {D}, {L} rows)")
+                               "(unmasked; head_dim 64 / 128 at most 64 rows, or head_dim 64 at most 80 rows; "
+                               f"got head_dim {D}, {L} rows)")
         if ring or (block_mask is None and getattr(kv_cache, "dev", None) is not None and offset > 0 and
                     K.decode_dev_supported(D, L)):
             # decode with the cache position on the device (one captured graph for every frame).  A
             # RingKVCache (sampling/stream.py) takes the kernels' ring forms: the new rows wrap modulo the
-            # capacity, the addresses never move
-            rope_kv, attend = (K.qk_rope_fwd_kv_ring, K.attn_decode_ring_fwd) if ring else \
-                (K.qk_rope_fwd_kv_dev, K.attn_decode_fwd)
+            # capacity, the addresses never move; a frame of 65 to 80 rows (the dit backbone's audio + video
+            # frame, head_dim 64) takes the five-tile wide attention
+            rope_kv, attend = (K.qk_rope_fwd_kv_ring, K.attn_decode_wide_ring_fwd if wide else
+                               K.attn_decode_ring_fwd) if ring else (K.qk_rope_fwd_kv_dev, K.attn_decode_fwd)
             kb, vb = kv_cache.bufs[self.layer_idx]
             q = torch.empty(B, L, d, device=qkv.device, dtype=torch.bfloat16)
             rope_kv(qkv, B, L, H, D, self.rope.cos, self.rope.sin, kv_cache.dev, q, kb, vb)

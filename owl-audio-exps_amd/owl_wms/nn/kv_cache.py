@@ -311,7 +311,10 @@ class RingKVCache(SingleKVCache):
     def rebase(self, shift_tokens, rope=None):
         """Lower every live key's RoPE position by `shift_tokens` (whole frames): each layer's cached K is
         re-rotated in place (V carries no position), then the offsets drop.  Valid for tables whose
-        angles are linear in the frame index (MotionRoPE, Audio1DRoPE)."""
+        angles are linear in the frame index: MotionRoPE, Audio1DRoPE, and OrthoRoPE, whose time axis
+        alone moves with the frame (angle a_r + f * delta).  The rotation is formed from two rows of the
+        table in hand, so the table need not be a prefix of a longer one (OrthoRoPE's is not).  Which
+        stream may rebase which table is the stream classes' choice (sampling/stream.py rebase_ropes)."""
         from .. import kernels as K
         rope = rope if rope is not None else self.rope
         assert rope is not None, "rebase needs the model's RoPE tables"

@@ -5,7 +5,7 @@ entry the reference resolves it to), ``av_stream`` (stream.py: the same sampler 
 RoPE rebase, for rollouts past ``n_frames``), ``audio_caching``, and the audio + video core's samplers
 ``av_window`` / ``av_causal`` / ``av_causal_no_cfg`` (av_window.py; the causal ones decode on the
 MMDiT's fused joint-frame path) and ``av_audio_stream`` (stream.py AVStreamSampler: endless audio + video
-streaming on a ring cache, each frame cached once).  The one-step variant is outside this build's scope (SURVEY.md
+streaming on a ring cache, each frame cached once, on either backbone of the core).  The one-step variant is outside this build's scope (SURVEY.md
 §8(f); the reference's import of it is broken).
 """
 

@@ -21,7 +21,9 @@ signature, for eval rollouts longer than ``config.n_frames``.
 
 ``AVFrameStream`` / ``AVStreamSampler`` (sampler id ``av_audio_stream``) are the same for the audio + video
 core (GameRFTAudioCore on the MMDiT): 65-row joint frames [64 video | 1 audio] on the ring forms of the
-joint-frame decode kernels, both modalities updated from one forward.
+joint-frame decode kernels, both modalities updated from one forward.  ``AVDiTFrameStream`` is the same
+for the core on the plain DiT (``backbone: dit``, the reference's configs/causvid.yml): the 65-row frame on
+the wide ring decode attention (owlk_attn_decode_wide_ring_fwd); the sampler id serves both backbones.
 """
 import torch
 
@@ -37,14 +39,15 @@ REBASE_ROPES = ("motion", "audio1d")  # angle tables linear in the frame index (
 
 
 class _RingStream:
-    """FrameStream and AVFrameStream over a tuple of latents -- (x,) for video, (video, audio) for audio +
-    video: the context pass into a RingKVCache, one frame per step (rebase, draws, Euler steps eager or
+    """FrameStream and the audio + video streams over a tuple of latents -- (x,) for video, (video, audio) for
+    audio + video: the context pass into a RingKVCache, one frame per step (rebase, draws, Euler steps eager or
     replayed from one captured step, zlerp, the cache-updating forward, eviction) and the captured step's
     life cycle.  A subclass supplies the core it accepts (its __init__), how one guided prediction is
     formed (_guided) and how the core is called with the cache (_forward)."""
 
     custom_schedule = None  # FrameStream's option
-    decoding = False  # transformer.enable_decoding() around a step (FrameStream)
+    decoding = False  # transformer.enable_decoding() around a step (FrameStream, AVDiTFrameStream)
+    rebase_ropes = REBASE_ROPES  # the rope_impl values the class may rebase (AVDiTFrameStream: ortho as well)
 
     def __init__(self, core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed):
         name, cfg = type(self).__name__, core.config
@@ -137,10 +140,10 @@ class _RingStream:
         if off + tpf <= rope.cos.shape[0]:
             return
         impl = str(getattr(core.config, "rope_impl", "ortho")).lower()
-        if impl not in REBASE_ROPES:
+        if impl not in self.rebase_ropes:
             raise RuntimeError(f"{type(self).__name__}: frame {self.frames_generated} would pass the "
-                               f"{rope.cos.shape[0]}-row RoPE table and rope_impl {impl!r} cannot be rebased (its "
-                               f"table is not linear in the frame index, nor prefix-stable); use one of {REBASE_ROPES}")
+                               f"{rope.cos.shape[0]}-row RoPE table and rope_impl {impl!r} cannot be rebased by this "
+                               f"stream; it rebases {self.rebase_ropes}")
         cache.rebase(off - len(cache), rope)
         self.rebases += 1
 
@@ -287,10 +290,11 @@ class StreamSampler:
         return torch.cat(latents, dim=1)
 
 
-class AVFrameStream(_RingStream):
-    """FrameStream for the audio + video core (GameRFTAudioCore, backbone ``mmdit``): ``pipe(controls) ->
-    (video frame, audio frame)`` for as long as the caller likes, on the ring forms of the MMDiT's
-    joint-frame decode kernels (MMDiTBlock._forward_ring_decode).
+class _AVRingStream(_RingStream):
+    """AVFrameStream and AVDiTFrameStream: FrameStream for the audio + video core (GameRFTAudioCore):
+    ``pipe(controls) -> (video frame, audio frame)`` for as long as the caller likes, 65-row joint frames
+    [64 video | 1 audio] on a RingKVCache.  A subclass names the core it accepts (_check_core) and, where
+    they differ from _RingStream's, ``decoding`` and ``rebase_ropes``.
 
     A persistent-cache sampler: every frame is noised (zlerp at noise_prev) and cached ONCE, as
     AVCachingSamplerV2 does for video.  It is not ``av_causal``'s algorithm, which re-noises the whole
@@ -309,16 +313,17 @@ class AVFrameStream(_RingStream):
     def __init__(self, core, n_steps: int = 16, cfg_scale: float = 1.3, noise_prev: float = 0.2,
                  max_cached_frames: int = 120, graphed: bool = False, ring_frames=None) -> None:
         cfg = core.config
-        D = cfg.d_model // cfg.n_heads
-        if cfg.backbone != "mmdit" or D != 64:
-            raise ValueError("AVFrameStream: needs the MMDiT joint-frame decode path (backbone 'mmdit', head_dim 64); "
-                             f"got backbone {cfg.backbone!r}, head_dim {D}")
+        self._check_core(cfg, cfg.d_model // cfg.n_heads)
         super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed)
         if ring_frames is not None and ring_frames < max_cached_frames + 1:
-            raise ValueError(f"AVFrameStream: ring_frames = {ring_frames} cannot hold max_cached_frames + 1 = "
-                             f"{max_cached_frames + 1} frames")
+            raise ValueError(f"{type(self).__name__}: ring_frames = {ring_frames} cannot hold max_cached_frames + 1 "
+                             f"= {max_cached_frames + 1} frames")
         if ring_frames is not None:
             self.ring_frames = ring_frames
+
+    def _check_core(self, cfg, D):
+        """ValueError, naming what it got, unless this class streams the core of config cfg (head_dim D)."""
+        raise NotImplementedError
 
     def _forward(self, cache, xs, t, mouse, btn):
         return self.core(*self._rep(*xs, t, mouse, btn), has_controls=self._hc, kv_cache=cache)
@@ -346,11 +351,48 @@ class AVFrameStream(_RingStream):
         return self._step(mouse_1, btn_1)
 
 
+class AVFrameStream(_AVRingStream):
+    """The MMDiT core (backbone ``mmdit``, head_dim 64), on the ring forms of the MMDiT's joint-frame decode
+    kernels (MMDiTBlock._forward_ring_decode)."""
+
+    def _check_core(self, cfg, D):
+        if cfg.backbone != "mmdit" or D != 64:
+            raise ValueError("AVFrameStream: needs the MMDiT joint-frame decode path (backbone 'mmdit', head_dim 64); "
+                             f"got backbone {cfg.backbone!r}, head_dim {D}")
+
+
+class AVDiTFrameStream(_AVRingStream):
+    """The dit-backbone core (the reference's configs/causvid.yml: ``game_rft_audio`` with ``backbone: dit``,
+    the audio token appended to each frame's video tokens through the plain DiT; head_dim 64, at most 80
+    tokens per frame), on ``owlk_qk_rope_fwd_kv_ring`` + the wide ring decode attention
+    (``owlk_attn_decode_wide_ring_fwd``, Attn._attend), ``DiT.enable_decoding()`` around a step.
+
+    It may rebase on OrthoRoPE (the reference's default) as well: the angle of token r of frame f is
+    a_r + f * delta -- only the time axis moves, linearly -- and owlk_rope_rebase forms its rotation from
+    two table rows, so it needs linearity only, not the prefix stability that OrthoRoPE's linspace time
+    axis lacks (tests/test_av_dit_stream_cpu.py has the bound)."""
+
+    decoding = True
+    rebase_ropes = ("motion", "audio1d", "ortho")
+
+    def _check_core(self, cfg, D):
+        if cfg.backbone != "dit" or D != 64 or not 0 < cfg.tokens_per_frame <= K.WIDE_DECODE_ROWS:
+            raise ValueError("AVDiTFrameStream: needs the DiT ring decode path (backbone 'dit', head_dim 64, at most "
+                             f"{K.WIDE_DECODE_ROWS} tokens per frame); got backbone {cfg.backbone!r}, head_dim {D}, "
+                             f"{cfg.tokens_per_frame} tokens per frame")
+
+
+def av_stream_cls(backbone):
+    """The audio + video stream class of a GameRFTAudioCore's backbone."""
+    return AVDiTFrameStream if backbone == "dit" else AVFrameStream
+
+
 class AVStreamSampler:
     """Sampler id ``av_audio_stream``: the causal audio + video samplers' call signature and return value
-    on an AVFrameStream, so a rollout may run past config.n_frames (MotionRoPE; OrthoRoPE streams to the
-    end of its table and then raises).  A persistent-cache sampler -- each frame noised and cached once --
-    not ``av_causal``'s re-noise-the-window-per-frame algorithm: the two are not comparable draw for
+    on the stream class of the model's backbone (av_stream_cls: AVFrameStream for ``mmdit``, AVDiTFrameStream
+    for ``dit``), so a rollout may run past config.n_frames (MotionRoPE; with OrthoRoPE the dit stream
+    rebases too, the MMDiT stream runs to the end of its table and then raises).  A persistent-cache
+    sampler -- each frame noised and cached once -- not ``av_causal``'s re-noise-the-window-per-frame algorithm: the two are not comparable draw for
     draw.  ``max_cached_frames`` None: the longest window the RoPE table leaves room to rebase in,
     ``config.n_frames - 2`` frames."""
 
@@ -371,8 +413,8 @@ class AVStreamSampler:
         cached = model.config.n_frames - 2 if self.max_cached_frames is None else self.max_cached_frames
         ext_mouse, ext_btn = batch_permute_to_length(mouse, btn, n + self.num_frames)
         vs, as_ = [video.clone()], [audio.clone()]
-        with AVFrameStream(model, self.n_steps, self.cfg_scale, self.noise_prev, cached,
-                           graphed=compile_on_decode) as stream:
+        with av_stream_cls(model.config.backbone)(model, self.n_steps, self.cfg_scale, self.noise_prev, cached,
+                                                  graphed=compile_on_decode) as stream:
             stream.start(video, audio, ext_mouse, ext_btn)
             for idx in range(self.num_frames):
                 i = n + idx

@@ -1,15 +1,16 @@
-"""Endless audio + video streaming (sampling/stream.py AVFrameStream: ring KV cache, ring joint-frame decode
-kernels, RoPE rebase) against av_causal(window_length = ctx + 1) at the same settings: wall ms per generated
-frame, eager and HIP graph, alternated in one process on configs/mmdit_v2.yml's MMDiT with weights as
-initialised and rope_impl motion (B = 1).
+"""Endless audio + video streaming (sampling/stream.py AVFrameStream / AVDiTFrameStream: ring KV cache, ring
+decode kernels, RoPE rebase) against av_causal(window_length = ctx + 1) at the same settings: wall ms per
+generated frame, eager and HIP graph, alternated in one process on configs/mmdit_v2.yml's sizes with weights
+as initialised (B = 1).  --backbone and --rope override the config's fields and select the stream class.
 
-    python tools/av_stream_bench.py [--ctx 15] [--cached 15] [--frames 48] [--steps 4] [--cfg 1.3]
-                                    [--table-frames 40] [--rounds 3]
+    python tools/av_stream_bench.py [--backbone mmdit|dit] [--rope motion|ortho] [--ctx 15] [--cached 15]
+                                    [--frames 48] [--steps 4] [--cfg 1.3] [--table-frames 40] [--rounds 3]
 
-The stream's run must hold at least 2 wraps of the ring and 1 rebase, so it runs on the first
---table-frames frames of the RoPE table (a bit-identical prefix: MotionRoPE tables are prefix-stable);
-av_causal, which refills its cache per frame, keeps the whole table.  Per-frame cost does not depend on the
-table length.
+The stream's run must hold at least 2 wraps of the ring and 1 rebase, so it runs on a RoPE table of
+--table-frames frames: for motion the first --table-frames frames of the model's table (a bit-identical
+prefix: MotionRoPE tables are prefix-stable), for ortho (not prefix-stable) the table of the same config
+with n_frames = --table-frames.  av_causal, which refills its cache per frame, keeps the whole table.
+Per-frame cost does not depend on the table length.
 
 Stream rows: every step() is timed on the host with a synchronize after it (a caller who shows the frame
 waits for it too); reported per round are the median over all frames and over the steady-state frames
@@ -19,7 +20,9 @@ tools/av_decode_bench.py forms its steady state.  None of av_causal's code diffe
 the stream was added, so its rows are also that commit's timing on the same box.
 
 Then the ring joint decode attention against the linear one on the same keys (1,040 and 16,640), alternated,
-timed with events.
+timed with events, and the wide ring decode attention (the dit backbone's) against the joint ring kernel
+(the same bits) and against attn_fwd unmasked over the same [cache | new] rows, which is what a dit-backbone
+decode step runs without a ring.
 """
 import argparse
 import os
@@ -30,6 +33,23 @@ import time
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "owl-audio-exps_amd")]
 import torch  # noqa: E402
+
+
+def alternated(fns, rounds, iters):
+    """name -> 'median us (min, max)' per call over `rounds` rounds of `iters` calls, the variants alternated
+    within a round, timed with events, after one warm-up round"""
+    res = {k: [] for k in fns}
+    for _ in range(rounds + 1):
+        for name, fn in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(iters):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            res[name].append(e0.elapsed_time(e1) * 1e3 / iters)
+    return {k: f"{statistics.median(v[1:]):.1f} us (min {min(v[1:]):.1f}, max {max(v[1:]):.1f})"
+            for k, v in res.items()}
 
 
 def attention_ab(H, D, rounds, iters=50):
@@ -56,27 +76,35 @@ def attention_ab(H, D, rounds, iters=50):
             a = [t.clone() for t in fns["ring"]()[:2]]
             b = fns["linear"]()[:2]
             same = all(torch.equal(x, y) for x, y in zip(a, b))
-            res = {k: [] for k in fns}
-            for _ in range(rounds + 1):  # the first round warms up
-                for name, fn in fns.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(iters):
-                        fn()
-                    e1.record()
-                    torch.cuda.synchronize()
-                    res[name].append(e0.elapsed_time(e1) * 1e3 / iters)
-            r, l = res["ring"][1:], res["linear"][1:]
-            print(f"joint decode attention, {keys} keys, B {B}, H {H}: ring {statistics.median(r):.1f} us "
-                  f"(min {min(r):.1f}, max {max(r):.1f}), linear {statistics.median(l):.1f} us (min {min(l):.1f}, "
-                  f"max {max(l):.1f}); same bits: {same}", flush=True)
+            res = alternated(fns, rounds, iters)
+            print(f"joint decode attention, {keys} keys, B {B}, H {H}: ring {res['ring']}, linear {res['linear']}; "
+                  f"same bits: {same}", flush=True)
+            # the wide ring kernel (one output, the dit backbone's) against the joint ring kernel, and against
+            # attn_fwd unmasked over the unrolled [cache | new] rows
+            ow = torch.empty(B, L, H * D, device="cuda", dtype=torch.bfloat16)
+            mask = K.FrameMask(1, None, False, 0, None)
+            fns = {"wide": lambda: K.attn_decode_wide_ring_fwd(q, kb, vb, H, D, st, L, 0, score_bound=bound, o=ow),
+                   "joint": fns["ring"],
+                   "attn_fwd": lambda: K.attn_fwd(q, kl, vl, H, D, mask, score_bound=bound)}
+            w = fns["wide"]()[0].clone()
+            same = torch.equal(w[:, :n0].reshape(B * n0, -1), a[0]) and \
+                torch.equal(w[:, n0:].reshape(B * n1, -1), a[1])
+            ref = fns["attn_fwd"]()[0].float()
+            err = ((w.float() - ref).norm() / ref.norm()).item()
+            res = alternated(fns, rounds, iters)
+            print(f"wide decode attention, {keys} keys, B {B}, H {H}: wide ring {res['wide']}, joint ring "
+                  f"{res['joint']}; same bits: {same}", flush=True)
+            print(f"wide decode attention, {keys} keys, B {B}, H {H}: wide ring {res['wide']}, attn_fwd unmasked "
+                  f"{res['attn_fwd']}; rel-L2 {err:.1e}", flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="configs/mmdit_v2.yml")
+    ap.add_argument("--backbone", choices=("mmdit", "dit"), default="mmdit")
+    ap.add_argument("--rope", choices=("motion", "ortho"), default="motion")
     ap.add_argument("--ctx", type=int, default=15)
-    ap.add_argument("--cached", type=int, default=15, help="AVFrameStream max_cached_frames")
+    ap.add_argument("--cached", type=int, default=15, help="the stream's max_cached_frames")
     ap.add_argument("--frames", type=int, default=48)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--cfg", type=float, default=1.3)
@@ -89,16 +117,25 @@ def main():
     from owl_wms.configs import Config
     from owl_wms.models import get_model_cls
     from owl_wms.sampling import get_sampler_cls
-    from owl_wms.sampling.stream import AVFrameStream
+    from owl_wms.nn.rope import get_rope_cls
+    from owl_wms.sampling.stream import av_stream_cls
     cfg = Config.from_yaml(os.path.join(REPO, args.config))
     mc = cfg.model
-    mc.rope_impl = "motion"
+    mc.backbone, mc.rope_impl = args.backbone, args.rope
+    stream_cls = av_stream_cls(mc.backbone)
     torch.manual_seed(0)
     model = get_model_cls(mc.model_id)(mc).cuda().eval()
     core, rope, tpf = model.core, model.core.transformer.rope, mc.tokens_per_frame
     full = (rope.cos, rope.sin)
-    short = tuple(t[:args.table_frames * tpf] for t in full)
     assert args.cached + 1 < args.table_frames <= mc.n_frames
+    if args.rope == "motion":
+        short = tuple(t[:args.table_frames * tpf] for t in full)
+    else:  # the table a model with n_frames = --table-frames carries
+        n_frames, mc.n_frames = mc.n_frames, args.table_frames
+        short_rope = get_rope_cls(args.rope)(mc).cuda()
+        mc.n_frames = n_frames
+        short = (short_rope.cos, short_rope.sin)
+        assert short[0].shape == (args.table_frames * tpf, full[0].shape[1])
     W, n = args.ctx + 1, args.ctx + args.frames
     # av_causal inpaints at the end of a window of W frames, W - 1 = ctx of them history: it takes W context
     # frames and re-noises the last ctx; the stream caches the same ctx frames once
@@ -107,8 +144,8 @@ def main():
     x, audio = xw[:, 1:], audiow[:, 1:]
     mouse = torch.randn(1, n, 2, device="cuda").bfloat16()
     btn = (torch.rand(1, n, mc.n_buttons, device="cuda") < 0.5).bfloat16()
-    print(f"{args.config} (rope_impl motion): B 1, ctx {args.ctx}, {args.steps} steps, cfg {args.cfg}; stream: "
-          f"max_cached_frames {args.cached}, {args.frames} frames, table {args.table_frames} frames; av_causal: "
+    print(f"{args.config} (backbone {mc.backbone}, rope_impl {mc.rope_impl}, {stream_cls.__name__}): B 1, ctx "
+          f"{args.ctx}, {args.steps} steps, cfg {args.cfg}; stream: max_cached_frames {args.cached}, {args.frames} frames, table {args.table_frames} frames; av_causal: "
           f"window {W}, {args.frames_a} / {args.frames_b} frames; {args.rounds} rounds, variants alternated",
           flush=True)
 
@@ -117,7 +154,7 @@ def main():
         try:
             per, rebased = [], []
             torch.manual_seed(1)
-            with AVFrameStream(core, args.steps, args.cfg, 0.2, args.cached, graphed=graphed) as s:
+            with stream_cls(core, args.steps, args.cfg, 0.2, args.cached, graphed=graphed) as s:
                 s.start(x, audio, mouse, btn)
                 torch.cuda.synchronize()
                 for i in range(args.frames):
