@@ -177,6 +177,17 @@ int owlk_qk_rope_fwd_kv_ring(const void* qkv, long ldq, long T, long L, int H, i
 int owlk_rope_rebase(void* kbuf, long ldk, long skb, long B, int H, int D, long start, long rows, long cap,
                      const float* cosb, const float* sinb, long ld_tab, long n_tab, long old_off, long new_off,
                      void* stream);
+/* Ring advance: a streamed frame's commit + eviction on the device, so a whole frame can be one captured
+ * graph (the reference's inference/causvid_pipeline.py:112-163 keeps its sliding window on the host).
+ * state is the int64 device vector {start, cached, offset, 0} the ring kernels read.  One launch:
+ *   cached += L; offset += L;  then, if cached > max_rows:  start = (start + L) mod cap; cached -= L
+ * -- RingKVCache.commit_device on every layer, then truncate(1, front=False) when over.  Host-checked
+ * (returns 1): L > 0, 0 < max_rows, max_rows + L <= cap, state non-null.  Device-side contract:
+ * 0 <= start < cap, cached >= 0, cached + L <= cap, offset >= 0; outside it the kernel writes cached = -1
+ * and leaves start and offset alone.  Every ring kernel treats a negative count as out of contract (NaN
+ * rows, nothing read or written), so a broken state poisons every later frame instead of being followed.
+ * One thread, ordinary loads and stores; stream order after the frame's last attention orders it. */
+int owlk_ring_advance(long* state, long L, long max_rows, long cap, void* stream);
 /* MMDiT decode form (mmattn.py:46-86): the joint frames [n0 video | n1 audio] read straight from the
  * two modalities' qkv GEMM outputs (joint row r of frame f of batch b: video row (b nf + f) n0 + r for
  * r < n0, else audio row (b nf + f) n1 + r - n0), table row tab_off + f (n0 + n1) + r.  q goes to a

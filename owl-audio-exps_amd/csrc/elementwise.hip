@@ -1097,6 +1097,45 @@ extern "C" int owlk_rope_rebase(void* kbuf, long ldk, long skb, long B, int H, i
   return owlk::check_launch("rope_rebase");
 }
 
+// Ring advance (owlk_ring_advance): one thread commits a streamed frame of L rows to the device state
+// {start, cached, offset} and evicts the oldest frame once more than max_rows are cached -- what
+// RingKVCache.commit_device on every layer, then truncate(1, front=False), do on the host
+// (causvid_pipeline.py's sliding window).  A state outside the contract is not followed: cached becomes
+// -1, which every ring kernel treats as out of contract (NaN rows, nothing read or written), and it
+// stays -1 under further advances.
+__global__ void ring_advance_k(long* __restrict__ state, long L, long max_rows, long cap) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const long start = state[0], cached = state[1], off = state[2];
+  // cached <= cap - L first, so cached + L cannot overflow; offset + L must not either
+  if (start < 0 || start >= cap || cached < 0 || cached > cap - L || off < 0 || off > INT64_MAX - L) {
+    state[1] = -1;
+    return;
+  }
+  long s = start, n = cached + L;
+  if (n > max_rows) {  // L <= cap (host-checked), so s + L < 2 cap: one conditional subtraction
+    s += L;
+    s = s < cap ? s : s - cap;
+    n -= L;
+  }
+  state[0] = s;
+  state[1] = n;
+  state[2] = off + L;
+}
+
+// The streamed frame's commit + eviction on the device, so that a whole frame -- Euler steps, re-noise,
+// the forward that writes the finished frame's rows, this -- is one captured graph
+// (sampling/stream.py graphed="frame"; the reference's inference/causvid_pipeline.py:112-163 does the
+// same bookkeeping on the host per call).  Stream order after the frame's last attention is all the
+// ordering it needs.
+extern "C" int owlk_ring_advance(long* state, long L, long max_rows, long cap, void* stream) {
+  OWLK_REQUIRE(state, "ring_advance: state pointer required");
+  OWLK_REQUIRE(L > 0 && max_rows > 0 && cap > 0 && max_rows <= cap - L,
+               "ring_advance: need L > 0, 0 < max_rows and max_rows + L <= cap (L=%ld max_rows=%ld cap=%ld)", L,
+               max_rows, cap);
+  hipLaunchKernelGGL(ring_advance_k, dim3(1), dim3(1), 0, (hipStream_t)stream, state, L, max_rows, cap);
+  return owlk::check_launch("ring_advance");
+}
+
 static int qk_rope_kv_launch(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
                              const float* sinb, long ld_tab, long n_tab, long tab_off, void* qo, long ldqo, long sqo,
                              void* ko, long ldko, long sko, void* vo, long ldvo, long svo, const long* state,

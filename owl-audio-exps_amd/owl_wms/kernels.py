@@ -393,6 +393,15 @@ def rope_rebase(kbuf, H, D, start, rows, cos, sin, old_off, new_off):
          kbuf.shape[1], ptr(cos), ptr(sin), cos.stride(0), cos.shape[0], int(old_off), int(new_off), stream())
 
 
+def ring_advance(state, L, max_rows, cap):
+    """In place on the device vector state int64 {start, cached, offset, 0}: a frame of L rows is committed
+    (cached += L, offset += L) and, once more than max_rows are cached, the oldest L rows are evicted
+    (start = (start + L) mod cap, cached -= L).  A state outside 0 <= start < cap, 0 <= cached,
+    cached + L <= cap, 0 <= offset gets cached = -1, which the ring kernels do not follow."""
+    assert state.dtype == torch.int64 and state.numel() >= 3 and state.is_cuda and state.is_contiguous()
+    call("owlk_ring_advance", ptr(state), int(L), int(max_rows), int(cap), stream())
+
+
 def mm_qk_rope_fwd_kv(qkv0, qkv1, B, nf, n0, n1, H, D, cos, sin, tab_off, q_out, k_out, v_out):
     """MMDiT decode form: the two modalities' qkv GEMM outputs (qkv0 [B nf n0, 3 H D] video, qkv1
     [B nf n1, 3 H D] audio) -> rotated q of the joint frames [n0 video | n1 audio] into q_out

@@ -282,6 +282,41 @@ class RingKVCache(SingleKVCache):
         self.len[layer_ind] += L
         self.offsets[layer_ind] += L
 
+    def advance(self, L, max_rows, device=True):
+        """A streamed frame of L rows, already written behind the window by the frame's last forward, is
+        committed and the oldest L rows are evicted once more than max_rows are cached:
+
+            len += L; offsets += L;  then, if len > max_rows:  start = (start + L) % capacity; len -= L
+
+        -- commit_device on every layer, then truncate(1, front=False) when over, as one rule.  It is
+        applied to the host mirror of every layer; with device=True the device vector follows by one
+        ``owlk_ring_advance`` launch (no host-to-device copy, so a captured frame holds it).  Under graph
+        capture only the launch is recorded: a capture executes nothing, so the mirror stays (the caller
+        advances it once per replay with device=False)."""
+        L, max_rows = int(L), int(max_rows)
+        assert L > 0 and 0 < max_rows and max_rows + L <= self.capacity, \
+            f"advance: need 0 < L, 0 < max_rows and max_rows + L <= capacity ({L}, {max_rows}, {self.capacity})"
+        if device:
+            from .. import kernels as K
+            assert self.dev is not None, "advance(device=True) after enable_device_state()"
+            K.ring_advance(self.dev, L, max_rows, self.capacity)
+            if torch.cuda.is_current_stream_capturing():
+                return
+        for i in range(self.config.n_layers):
+            assert self.len[i] + L <= self.capacity, "ring capacity exceeded (evict before committing)"
+            self.len[i] += L
+            self.offsets[i] += L
+            if self.len[i] > max_rows:
+                self.start[i] = (self.start[i] + L) % self.capacity
+                self.len[i] -= L
+
+    def device_state(self):
+        """(start, cached, offset) read back from the device vector (a synchronising copy): for tests and
+        for a stream's close(), which compares it with the host mirror."""
+        assert self.dev is not None, "device_state after enable_device_state()"
+        s, n, o, _ = self.dev.tolist()
+        return s, n, o
+
     def extend_slots(self, layer_ind, L, like):
         raise RuntimeError("RingKVCache: the new rows may wrap, so there is no slot view; the ring rope kernel "
                            "(kernels.qk_rope_fwd_kv_ring) writes them")

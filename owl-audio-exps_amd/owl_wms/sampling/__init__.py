@@ -2,7 +2,8 @@
 
 Implemented on libowlk's KV-cache decode path: ``av_caching`` (AVCachingSamplerV2, the registry
 entry the reference resolves it to), ``av_stream`` (stream.py: the same sampler on a ring cache with a
-RoPE rebase, for rollouts past ``n_frames``), ``audio_caching``, and the audio + video core's samplers
+RoPE rebase, for rollouts past ``n_frames``), ``audio_caching``, ``audio_stream`` (stream.py
+AudioStreamSampler: the audio sampler on a ring cache, for rollouts past ``n_frames``), and the audio + video core's samplers
 ``av_window`` / ``av_causal`` / ``av_causal_no_cfg`` (av_window.py; the causal ones decode on the
 MMDiT's fused joint-frame path) and ``av_audio_stream`` (stream.py AVStreamSampler: endless audio + video
 streaming on a ring cache, each frame cached once, on either backbone of the core).  The one-step variant is outside this build's scope (SURVEY.md
@@ -29,6 +30,9 @@ def get_sampler_cls(sampler_id):
     if sampler_id == "audio_caching":
         from .audio_caching import AudioCachingSampler
         return AudioCachingSampler
+    if sampler_id == "audio_stream":
+        from .stream import AudioStreamSampler
+        return AudioStreamSampler
     if sampler_id in AV_WINDOW_SAMPLERS:
         from . import av_window
         return getattr(av_window, AV_WINDOW_SAMPLERS[sampler_id])

@@ -35,7 +35,11 @@ def euler_dt(n_steps, custom_schedule, like):
     return torch.tensor(get_deltas(list(custom_schedule)), device=like.device, dtype=torch.float32)
 
 
+def renoise(x, z, alpha):
+    """x re-noised to level alpha with the noise z in hand (a captured frame reads z from a static buffer)"""
+    return x * (1.0 - alpha) + z * alpha
+
+
 def zlerp(x, alpha):
     """x re-noised to level alpha: one torch.randn_like draw"""
-    z = torch.randn_like(x)
-    return x * (1.0 - alpha) + z * alpha
+    return renoise(x, torch.randn_like(x), alpha)

@@ -4,7 +4,8 @@ owl_wms that captures a graph.
 ``capture`` records a callable on a side stream.  ``StepGraph`` is the pattern the samplers share: ONE
 Euler step on static buffers, replayed for every step -- the cache is read-only while a frame is
 denoised, so every step launches the same kernels on the same buffers; same kernels and arithmetic as
-the eager loop (the reference's ``compile_on_decode`` switch).
+the eager loop (the reference's ``compile_on_decode`` switch).  ``FrameGraph`` is the
+ring streams' other pattern: a whole streamed frame, the cache's commit included, as one graph.
 
 What a caller has to keep to (the graph knows nothing about samplers, models or RoPE):
 
@@ -68,6 +69,34 @@ class StepGraph:
     def state(self):
         """clones of the state buffers, in `state`'s order"""
         return tuple(self.bufs[k].clone() for k in self._state)
+
+    def release(self):
+        _release_graph(self.graph)
+
+
+class FrameGraph:
+    """One whole streamed frame ``frame(inputs) -> outputs`` captured on static buffers (the ring streams'
+    ``graphed="frame"``): `inputs` is a dict of named tensors, cloned here into the static buffers the
+    frame function gets under the same names; its outputs (a tuple of tensors) stay in the graph's pool
+    and are cloned out per replay.  Everything that changes between frames is either an input or device
+    state the frame's own kernels read and advance (the ring position), so a frame is copy-in, one
+    replay, clone-out.  The capture executes nothing."""
+
+    def __init__(self, frame, inputs, pool=None):
+        self.bufs = {k: v.clone() for k, v in inputs.items()}
+        self.graph, self.out = capture(lambda: tuple(frame(self.bufs)), pool)
+
+    def load(self, **tensors):
+        """fresh values for the named buffers (a new frame's noise and controls)"""
+        for k, v in tensors.items():
+            self.bufs[k].copy_(v)
+
+    def replay(self):
+        self.graph.replay()
+
+    def outputs(self):
+        """clones of the frame function's outputs, in its order"""
+        return tuple(o.clone() for o in self.out)
 
     def release(self):
         _release_graph(self.graph)

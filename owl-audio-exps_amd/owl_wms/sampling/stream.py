@@ -24,6 +24,14 @@ core (GameRFTAudioCore on the MMDiT): 65-row joint frames [64 video | 1 audio] o
 joint-frame decode kernels, both modalities updated from one forward.  ``AVDiTFrameStream`` is the same
 for the core on the plain DiT (``backbone: dit``, the reference's configs/causvid.yml): the 65-row frame on
 the wide ring decode attention (owlk_attn_decode_wide_ring_fwd); the sampler id serves both backbones.
+``AudioStream`` / ``AudioStreamSampler`` (sampler id ``audio_stream``) are the same for the audio core
+(AudioRFTCore): one token per frame, unconditional, no controls.
+
+``graphed`` on every class: False (eager), True (one captured Euler step replayed for every step of every
+frame; the forward that commits the finished frame stays eager) or "frame" -- the whole frame as one graph,
+the commit and the eviction included: the ring position {start, cached, offset} is advanced on the device by
+``owlk_ring_advance`` (RingKVCache.advance), the host keeps an exact mirror of it, and ``close()`` compares
+the two.  The three modes give the same bits.
 """
 import torch
 
@@ -32,25 +40,34 @@ from ..nn.attn import check_rope_rows
 from ..nn.kv_cache import RingKVCache
 from ..utils import batch_permute_to_length
 from .av_caching_v2 import guided_velocity
-from .schedulers import euler_dt, zlerp
-from .step_graph import StepGraph
+from .schedulers import euler_dt, renoise, zlerp
+from .step_graph import FrameGraph, StepGraph
 
 REBASE_ROPES = ("motion", "audio1d")  # angle tables linear in the frame index (prefix-stable)
 
 
+def graph_mode(compile_on_decode, frame_graph):
+    """A sampler's ``compile_on_decode`` / ``frame_graph`` pair -> a stream's ``graphed``."""
+    return "frame" if compile_on_decode and frame_graph else compile_on_decode
+
+
 class _RingStream:
     """FrameStream and the audio + video streams over a tuple of latents -- (x,) for video, (video, audio) for
-    audio + video: the context pass into a RingKVCache, one frame per step (rebase, draws, Euler steps eager or
-    replayed from one captured step, zlerp, the cache-updating forward, eviction) and the captured step's
-    life cycle.  A subclass supplies the core it accepts (its __init__), how one guided prediction is
-    formed (_guided) and how the core is called with the cache (_forward)."""
+    audio + video, (x,) for audio: the context pass into a RingKVCache, one frame per step (rebase, draws, Euler
+    steps eager or replayed from one captured step, zlerp, the cache-updating forward, eviction -- or all of it
+    after the draws as one captured frame, _frame) and the captured step's or frame's life cycle.  A subclass
+    supplies the core it accepts (its __init__), how one guided prediction is formed (_guided) and how the core
+    is called with the cache (_forward)."""
 
     custom_schedule = None  # FrameStream's option
     decoding = False  # transformer.enable_decoding() around a step (FrameStream, AVDiTFrameStream)
     rebase_ropes = REBASE_ROPES  # the rope_impl values the class may rebase (AVDiTFrameStream: ortho as well)
 
-    def __init__(self, core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed):
+    def __init__(self, core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed, ring_frames=None):
         name, cfg = type(self).__name__, core.config
+        if graphed not in (False, True, "frame"):
+            raise ValueError(f"{name}: graphed must be False, True (one captured Euler step) or 'frame' (the whole "
+                             f"frame captured); got {graphed!r}")
         if max_cached_frames < 1:
             raise ValueError(f"{name}: max_cached_frames must be at least 1")
         if max_cached_frames + 1 >= cfg.n_frames:
@@ -62,10 +79,15 @@ class _RingStream:
         self.cfg_scale = cfg_scale
         self.noise_prev = noise_prev
         self.max_cached_frames = max_cached_frames
-        self.ring_frames = max_cached_frames + 1  # the ring's size in frames
+        if ring_frames is not None and ring_frames < max_cached_frames + 1:
+            raise ValueError(f"{name}: ring_frames = {ring_frames} cannot hold max_cached_frames + 1 "
+                             f"= {max_cached_frames + 1} frames")
+        # the ring's size in frames; a larger ring wraps later and changes no bit of the output
+        self.ring_frames = max_cached_frames + 1 if ring_frames is None else ring_frames
         self.graphed = graphed
         self.frames_generated = 0
         self.rebases = 0
+        self.graph_replays = 0
         self.kv_cache = None
         self._step_graph = None
         self._pool = None
@@ -74,14 +96,23 @@ class _RingStream:
         return self
 
     def __exit__(self, *exc):
-        self.close()
+        self.close(check=exc[0] is None)  # an error on its way out is not replaced by the state check's
         return False
 
-    def close(self):
-        """Release the captured step (after its queued replays have run)."""
+    def close(self, check=True):
+        """Release the captured step or frame (after its queued replays have run).  In frame mode the ring
+        position moved on the device alone: it is read back here and compared with the host mirror, which
+        is where a state the kernels refused to follow (cached = -1, NaN frames since) surfaces."""
         if self._step_graph is not None:
             self._step_graph.release()
         self._step_graph = None
+        cache = self.kv_cache
+        if check and self.graphed == "frame" and cache is not None and cache.dev is not None:
+            dev, host = cache.device_state(), (cache.start[0], len(cache), cache.get_offset(0))
+            if dev != host:
+                raise RuntimeError(f"{type(self).__name__}: the ring position on the device (start, cached, offset) "
+                                   f"= {dev} differs from the host mirror {host} after {self.frames_generated} "
+                                   "frames; a count of -1 marks a state the ring kernels refused to follow")
 
     def _cfg(self):
         return self.cfg_scale != 1.0
@@ -120,13 +151,15 @@ class _RingStream:
         noisy = tuple(zlerp(x, self.noise_prev) for x in latents)
         ts = latents[0].new_full((B, init_len), self.noise_prev)
         cache.enable_cache_updates()
-        self._forward(cache, noisy, ts, mouse[:, :init_len], btn[:, :init_len])
+        # a core without controls (AudioStream) passes None for both
+        self._forward(cache, noisy, ts, *(c if c is None else c[:, :init_len] for c in (mouse, btn)))
         cache.disable_cache_updates()
         cache.enable_device_state()
         self._like, self._t1 = tuple(x[:, :1] for x in latents), ts[:, :1]
         self.kv_cache = cache
         self.frames_generated = 0
         self.rebases = 0
+        self.graph_replays = 0
         return self
 
     # ------------------------------------------------------------------ one frame
@@ -182,12 +215,61 @@ class _RingStream:
             # step's forward does (the kernels would only poison the rows with NaN)
             check_rope_rows(self.core.transformer.rope, self.kv_cache.get_offset(0),
                             self.core.config.tokens_per_frame)
-            # the frame's state and controls; any other input (null controls: zeros) stays as captured
-            sg.load(**dict(zip(names, xs)), t=t, mouse=ctrl["mouse"], btn=ctrl["btn"])
+            # the frame's state and whatever _controls returns
+            sg.load(**dict(zip(names, xs)), t=t, **ctrl)
         for t_idx in range(first, self.n_steps):
             sg.replay(dt[t_idx])
+        self.graph_replays += self.n_steps - first
         *xs, t = sg.state()
         return tuple(xs), t
+
+    def _frame(self, s):
+        """graphed="frame": the whole frame as one function of the named tensors s -- the start noise x{i},
+        the re-noise draws z{i}, the time t (ones) and the controls -- with nothing decided on the host:
+        the n_steps Euler steps (dt from the persistent self._dt), the finished frame copied out, the
+        re-noise, the forward on the re-noised frame and the ring position's advance on the device
+        (owlk_ring_advance).  On the ring path a forward writes its rows behind the window whether or not
+        cache updates are enabled -- should_update only moves the host bookkeeping -- so the last forward
+        is an ordinary decode forward and `advance` stands for commit_device + sync_device_state +
+        truncate.  Eager it also advances the host mirror; captured it executes nothing and the mirror
+        stays (RingKVCache.advance)."""
+        n, tpf = len(self._like), self.core.config.tokens_per_frame
+        xs, t = tuple(s[f"x{i}"] for i in range(n)), s["t"]
+        own = {"t"} | {f"{c}{i}" for c in "xz" for i in range(n)}
+        ctrl = {k: v for k, v in s.items() if k not in own}  # what _controls returned
+        for t_idx in range(self.n_steps):
+            xs, t = self._euler_step(xs, t, ctrl, self._dt[t_idx])
+        frame = tuple(x.clone() for x in xs)
+        noisy = tuple(renoise(x, s[f"z{i}"], self.noise_prev) for i, x in enumerate(xs))
+        t_noisy = torch.ones_like(t) * self.noise_prev
+        self._forward(self.kv_cache, noisy, t_noisy, ctrl.get("mouse"), ctrl.get("btn"))
+        self.kv_cache.advance(tpf, self.max_cached_frames * tpf)
+        return frame
+
+    def _graphed_frame(self, xs, t, ctrl):
+        """One frame in frame mode.  The noise is drawn here, outside the graph, in the other modes' order
+        (the start noise xs came first, now one re-noise draw per latent; they draw nothing in between).
+        Frame 0 runs _frame eagerly (bf16 weight copies, workspaces outside the graph pool); frame 1
+        captures it (a FrameGraph); from then on a frame is copy-in, one replay, clone-out, and the host
+        mirror of the ring position follows by the same rule (exact: the rule is deterministic)."""
+        cache, tpf = self.kv_cache, self.core.config.tokens_per_frame
+        zs = tuple(torch.randn_like(x) for x in self._like)
+        s = {**{f"x{i}": x for i, x in enumerate(xs)}, **{f"z{i}": z for i, z in enumerate(zs)}, "t": t, **ctrl}
+        if self.frames_generated == 0:
+            return self._frame(s)
+        # the replayed frame reads its positions from the device: check them here as an eager forward does
+        check_rope_rows(self.core.transformer.rope, cache.get_offset(0), tpf)
+        fg = self._step_graph
+        if fg is None:
+            if self._pool is None:
+                self._pool = torch.cuda.graph_pool_handle()
+            fg = self._step_graph = FrameGraph(self._frame, s, self._pool)
+        else:
+            fg.load(**s)
+        fg.replay()
+        cache.advance(tpf, self.max_cached_frames * tpf, device=False)
+        self.graph_replays += 1
+        return fg.outputs()
 
     @torch.no_grad()
     def _step(self, mouse_1, btn_1):
@@ -204,6 +286,13 @@ class _RingStream:
         ctrl = self._controls(mouse_1, btn_1)
         if self.decoding:
             core.transformer.enable_decoding()
+        if self.graphed == "frame":
+            try:
+                frame = self._graphed_frame(xs, t, ctrl)
+            finally:
+                core.transformer.disable_decoding()
+            self.frames_generated += 1
+            return frame
         try:
             xs, t = self._denoise(xs, t, ctrl)
             frame = tuple(x.clone() for x in xs)
@@ -228,8 +317,8 @@ class FrameStream(_RingStream):
     decoding = True
 
     def __init__(self, core, n_steps: int = 16, cfg_scale: float = 1.3, noise_prev: float = 0.2,
-                 max_cached_frames: int = 120, custom_schedule=None, graphed: bool = False) -> None:
-        super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed)
+                 max_cached_frames: int = 120, custom_schedule=None, graphed=False, ring_frames=None) -> None:
+        super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed, ring_frames)
         cfg = core.config
         D = cfg.d_model // cfg.n_heads
         if cfg.backbone != "dit" or not K.decode_dev_supported(D, cfg.tokens_per_frame):
@@ -266,13 +355,14 @@ class StreamSampler:
     RoPE table leaves room to rebase in, ``config.n_frames - 2`` frames."""
 
     def __init__(self, n_steps: int = 16, cfg_scale: float = 1.3, num_frames: int = 60, noise_prev: float = 0.2,
-                 max_window=None, custom_schedule=None) -> None:
+                 max_window=None, custom_schedule=None, frame_graph: bool = False) -> None:
         self.n_steps = n_steps
         self.cfg_scale = cfg_scale
         self.num_frames = num_frames
         self.noise_prev = noise_prev
         self.max_window = max_window
         self.custom_schedule = custom_schedule
+        self.frame_graph = frame_graph  # compile_on_decode captures the whole frame, not one Euler step
 
     @torch.no_grad()
     def __call__(self, model, x, mouse, btn, compile_on_decode=False):
@@ -282,7 +372,7 @@ class StreamSampler:
         num_frames = min(self.num_frames, mouse.size(1) - init_len)
         latents = [x.clone()]
         with FrameStream(model, self.n_steps, self.cfg_scale, self.noise_prev, cached, self.custom_schedule,
-                         graphed=compile_on_decode) as stream:
+                         graphed=graph_mode(compile_on_decode, self.frame_graph)) as stream:
             stream.start(x, mouse, btn)
             for idx in range(num_frames):
                 i = init_len + idx
@@ -314,12 +404,7 @@ class _AVRingStream(_RingStream):
                  max_cached_frames: int = 120, graphed: bool = False, ring_frames=None) -> None:
         cfg = core.config
         self._check_core(cfg, cfg.d_model // cfg.n_heads)
-        super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed)
-        if ring_frames is not None and ring_frames < max_cached_frames + 1:
-            raise ValueError(f"{type(self).__name__}: ring_frames = {ring_frames} cannot hold max_cached_frames + 1 "
-                             f"= {max_cached_frames + 1} frames")
-        if ring_frames is not None:
-            self.ring_frames = ring_frames
+        super().__init__(core, n_steps, cfg_scale, noise_prev, max_cached_frames, graphed, ring_frames)
 
     def _check_core(self, cfg, D):
         """ValueError, naming what it got, unless this class streams the core of config cfg (head_dim D)."""
@@ -397,12 +482,13 @@ class AVStreamSampler:
     ``config.n_frames - 2`` frames."""
 
     def __init__(self, n_steps: int = 16, cfg_scale: float = 1.3, num_frames: int = 60, noise_prev: float = 0.2,
-                 max_cached_frames=None) -> None:
+                 max_cached_frames=None, frame_graph: bool = False) -> None:
         self.n_steps = n_steps
         self.cfg_scale = cfg_scale
         self.num_frames = num_frames
         self.noise_prev = noise_prev
         self.max_cached_frames = max_cached_frames
+        self.frame_graph = frame_graph  # compile_on_decode captures the whole frame, not one Euler step
 
     @torch.no_grad()
     def __call__(self, model, video, audio, mouse, btn, decode_fn=None, audio_decode_fn=None, image_scale=1,
@@ -414,7 +500,7 @@ class AVStreamSampler:
         ext_mouse, ext_btn = batch_permute_to_length(mouse, btn, n + self.num_frames)
         vs, as_ = [video.clone()], [audio.clone()]
         with av_stream_cls(model.config.backbone)(model, self.n_steps, self.cfg_scale, self.noise_prev, cached,
-                                                  graphed=compile_on_decode) as stream:
+                                                  graphed=graph_mode(compile_on_decode, self.frame_graph)) as stream:
             stream.start(video, audio, ext_mouse, ext_btn)
             for idx in range(self.num_frames):
                 i = n + idx
@@ -427,3 +513,76 @@ class AVStreamSampler:
         if audio_decode_fn is not None:
             audio = audio_decode_fn(audio * audio_scale)
         return x, audio, ext_mouse, ext_btn
+
+
+class AudioStream(_RingStream):
+    """The audio core (AudioRFTCore, the reference's configs/audio.yml): ``pipe() -> token`` for as long as
+    the caller likes.  Unconditional, one token per frame, no CFG and no controls: AudioCachingSampler
+    (audio_caching.py) turned inside out on a RingKVCache -- the same context caching, Euler steps and torch
+    draws in the same order -- on ``owlk_qk_rope_fwd_kv_ring`` + ``owlk_attn_decode_ring_fwd`` at one query
+    row, local layers on the last ``local_window`` tokens.  It rebases on Audio1DRoPE (and MotionRoPE), so
+    it runs past the RoPE table, and its one-token forwards -- launch-bound, n_steps + 1 per token -- are
+    what a captured step or frame removes most of."""
+
+    decoding = True
+
+    def __init__(self, core, n_steps: int = 16, noise_prev: float = 0.2, max_cached_frames: int = 120,
+                 custom_schedule=None, graphed=False, ring_frames=None) -> None:
+        super().__init__(core, n_steps, 1.0, noise_prev, max_cached_frames, graphed, ring_frames)
+        cfg = core.config
+        D = cfg.d_model // cfg.n_heads
+        if cfg.backbone != "dit" or cfg.tokens_per_frame != 1 or not K.decode_dev_supported(D, 1):
+            raise ValueError("AudioStream: needs the DiT device-state decode path (head_dim 64 or 128) at one token "
+                             f"per frame; got backbone {cfg.backbone!r}, head_dim {D}, {cfg.tokens_per_frame} tokens "
+                             "per frame")
+        self.custom_schedule = custom_schedule
+
+    def _forward(self, cache, xs, t, mouse, btn):
+        return self.core(xs[0], t, doc_id=None, kv_cache=cache)
+
+    def _controls(self, mouse_1, btn_1):
+        return {}
+
+    def _guided(self, xs, t, ctrl):
+        return (self._forward(self.kv_cache, xs, t, None, None),)
+
+    def start(self, x):
+        """Cache the context tokens x [b, n, c], as AudioCachingSampler does (zlerp at noise_prev)."""
+        return self._start((x,), None, None)
+
+    def step(self):
+        """One new token -> [b, 1, c] (_RingStream._step)."""
+        return self._step(None, None)[0]
+
+
+class AudioStreamSampler:
+    """Sampler id ``audio_stream``: AudioCachingSampler's call signature and return value on an AudioStream,
+    so a rollout may run past config.n_frames.  ``max_window`` counts as that sampler's does (list entries,
+    the context as one): the stream caches ``max_window + init_len - 1`` tokens.  None: the longest window
+    the RoPE table leaves room to rebase in, ``config.n_frames - 2`` tokens.  ``compile_on_decode`` replays
+    one captured Euler step, with ``frame_graph`` one captured token."""
+
+    def __init__(self, n_steps: int = 16, num_tokens: int = 120, noise_prev: float = 0.2, custom_schedule=None,
+                 max_window=None, frame_graph: bool = False) -> None:
+        self.n_steps = n_steps
+        self.num_tokens = num_tokens
+        self.noise_prev = noise_prev
+        self.custom_schedule = custom_schedule
+        self.max_window = max_window
+        self.frame_graph = frame_graph
+
+    @torch.no_grad()
+    def __call__(self, model, x, decode_fn=None, vae_scale=1.0, compile_on_decode=False):
+        """model: an AudioRFTCore; x [b, init_len, c] -> [b, init_len + num_tokens, c] (+ waveforms)."""
+        init_len = x.size(1)
+        cached = model.config.n_frames - 2 if self.max_window is None else self.max_window + init_len - 1
+        latents = [x.clone()]
+        with AudioStream(model, self.n_steps, self.noise_prev, cached, self.custom_schedule,
+                         graphed=graph_mode(compile_on_decode, self.frame_graph)) as stream:
+            stream.start(x)
+            for _ in range(self.num_tokens):
+                latents.append(stream.step())
+        full = torch.cat(latents, dim=1)
+        if decode_fn is not None:
+            return full, decode_fn(full * vae_scale)
+        return full

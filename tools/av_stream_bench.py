@@ -1,6 +1,7 @@
 """Endless audio + video streaming (sampling/stream.py AVFrameStream / AVDiTFrameStream: ring KV cache, ring
 decode kernels, RoPE rebase) against av_causal(window_length = ctx + 1) at the same settings: wall ms per
-generated frame, eager and HIP graph, alternated in one process on configs/mmdit_v2.yml's sizes with weights
+generated frame, eager and HIP graph (one captured Euler step; for the stream also graphed="frame", the whole
+frame as one graph), alternated in one process on configs/mmdit_v2.yml's sizes with weights
 as initialised (B = 1).  --backbone and --rope override the config's fields and select the stream class.
 
     python tools/av_stream_bench.py [--backbone mmdit|dit] [--rope motion|ortho] [--ctx 15] [--cached 15]
@@ -112,6 +113,7 @@ def main():
     ap.add_argument("--frames-a", type=int, default=3)
     ap.add_argument("--frames-b", type=int, default=9)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--skip-attention", action="store_true", help="the streams only, not the attention kernels' A/B")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "av_stream_bench needs a GPU"
     from owl_wms.configs import Config
@@ -167,7 +169,8 @@ def main():
                 evictions = max(0, args.ctx + args.frames - args.cached)
                 wraps = evictions // (args.cached + 1)
                 rows = {kb.shape[1] for kb, _ in s.kv_cache.bufs}
-                full_from = max(1, args.cached - args.ctx + 1)  # the ring is full; frame 0 is eager / captures
+                # the ring is full; frame 0 is eager / captures the step, frame 1 captures the frame
+                full_from = max(2 if graphed == "frame" else 1, args.cached - args.ctx + 1)
                 steady = [t for t, rb in list(zip(per, rebased))[full_from:] if not rb]
                 reb = [t for t, rb in zip(per, rebased) if rb]
                 note = (f"{wraps} wraps, {s.rebases} rebases (rebase frames {', '.join(f'{t:.2f}' for t in reb)} ms), "
@@ -190,6 +193,7 @@ def main():
         return ts[1] / args.frames_b, steady, None, f"{W * tpf} cache rows per layer, refilled per frame"
 
     variants = (("stream eager", run_stream, False), ("stream graph", run_stream, True),
+                ("stream frame", run_stream, "frame"),
                 ("av_causal eager", run_causal, False), ("av_causal graph", run_causal, True))
     for name, fn, graphed in variants:  # warm-up of each
         fn(graphed)
@@ -208,7 +212,11 @@ def main():
     for mode in ("eager", "graph"):
         a, b = statistics.median(res[f"stream {mode}"]), statistics.median(res[f"av_causal {mode}"])
         print(f"{mode}: stream / av_causal = {a / b:.3f} (steady medians)", flush=True)
-    attention_ab(mc.n_heads, mc.d_model // mc.n_heads, args.rounds)
+    a, b = statistics.median(res["stream frame"]), statistics.median(res["stream graph"])
+    print(f"stream frame / stream graph = {a / b:.3f} (steady medians; the graph column is the code of the commit "
+          "before the frame mode)", flush=True)
+    if not args.skip_attention:
+        attention_ab(mc.n_heads, mc.d_model // mc.n_heads, args.rounds)
 
 
 if __name__ == "__main__":

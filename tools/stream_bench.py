@@ -1,6 +1,7 @@
 """Endless streaming (sampling/stream.py FrameStream: ring KV cache + RoPE rebase) against
 AVCachingSamplerV2(max_window=...) at the same settings: wall ms per generated frame, eager and HIP-graph
-replay, alternated in one process on a config's model with random-init weights (N = 1).
+replay (for the stream also graphed="frame", the whole frame as one graph), alternated in one process on a
+config's model with random-init weights (N = 1).
 
     python tools/stream_bench.py [--config configs/dit_v4.yml] [--ctx 8] [--cached 120] [--frames 360]
                                  [--steps 16] [--cfg 1.0] [--table-frames 256] [--reps 2]
@@ -95,15 +96,25 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) * 1e3 / args.frames, None, f"{(n + 1) * tpf} rows per layer"
 
-    res = {}
+    res, steadies = {}, {}
+    modes = {False: "eager", True: "graph", "frame": "frame"}
     for rep in range(args.reps):
-        for graphed in (False, True):
-            for name, fn in (("stream", run_stream), ("sampler", run_sampler)):
+        for graphed, mode in modes.items():
+            # "frame" (the whole frame as one graph) is a mode of the stream alone
+            for name, fn in (("stream", run_stream), ("sampler", run_sampler))[:1 if graphed == "frame" else 2]:
                 total, steady, note = fn(graphed)
                 res.setdefault((name, graphed), []).append(total)
-                mode = "graph" if graphed else "eager"
-                st = f", steady-state median {steady:.2f} ms" if steady is not None else ""
+                st = ""
+                if steady is not None:
+                    steadies.setdefault(mode, []).append(steady)
+                    st = f", steady-state median {steady:.2f} ms"
                 print(f"rep {rep} {name:7s} {mode}: {total:.2f} ms per generated frame{st} ({note})", flush=True)
+    for mode, v in steadies.items():
+        print(f"stream {mode}: steady-state {statistics.median(v):.2f} ms per generated frame (min {min(v):.2f}, max "
+              f"{max(v):.2f} over {args.reps} reps)", flush=True)
+    ratio = statistics.median(steadies["frame"]) / statistics.median(steadies["graph"])
+    print(f"stream frame / stream graph = {ratio:.3f} (steady-state medians; the graph column is the code of the "
+          "commit before the frame mode)", flush=True)
     for graphed in (False, True):
         mode = "graph" if graphed else "eager"
         a, b = res[("stream", graphed)], res[("sampler", graphed)]
