@@ -188,6 +188,30 @@ int owlk_rope_rebase(void* kbuf, long ldk, long skb, long B, int H, int D, long 
  * rows, nothing read or written), so a broken state poisons every later frame instead of being followed.
  * One thread, ordinary loads and stores; stream order after the frame's last attention orders it. */
 int owlk_ring_advance(long* state, long L, long max_rows, long cap, void* stream);
+/* Slot forms of the three ring entries, for many sessions in one batch (sampling/stream_pool.py StreamPool;
+ * the reference's inference/causvid_pipeline.py:112-163 serves one session per pipeline and set of weights).
+ * state is an int64 device array [n_slots, 4], row s = {start, cached tokens, rope offset, live}; batch row b
+ * follows row b mod n_slots, so with CFG the 2 n_slots batch rows [cond | uncond] of the cache pair up on one
+ * row per session.  Per slot:
+ *   live (live != 0), inside the single-state contract: the single-state entry's arithmetic and bits on that
+ *     slot's batch rows with that row as its state (the same kernel body);
+ *   idle (live == 0): nothing of the cache or the table is read or written; zero q rows, zero o rows, lse -inf;
+ *     the advance leaves the row alone;
+ *   live outside the contract: as the single-state entries, for that slot alone -- NaN q rows, NaN o rows and
+ *     lse, nothing read or written; the advance sets that row's cached = -1.
+ * No slot's state reaches another slot's rows.  Rebase stays per slot on the host: owlk_rope_rebase on the
+ * slot's batch rows (kbuf + slot * skb, batch stride n_slots * skb), then the row rewritten between replays.
+ *
+ * owlk_qk_rope_fwd_kv_ring_slots (attn.py:83-107 cache branch): owlk_qk_rope_fwd_kv_ring's arguments with
+ * n_slots after state; T / L batch rows, a multiple of n_slots (else returns 1). */
+int owlk_qk_rope_fwd_kv_ring_slots(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
+                                   const float* sinb, long ld_tab, long n_tab, const long* state, long n_slots,
+                                   void* qo, long ldqo, long sqo, void* kbuf, long ldk, long skb, void* vbuf,
+                                   long ldv, long svb, long cap, void* stream);
+/* owlk_ring_advance per live row of state [n_slots, 4] (causvid_pipeline.py:112-163, the sliding window of
+ * every session at once): one launch, thread s on row s, ordinary loads and stores; the rule, the
+ * host-checked arguments (plus 0 < n_slots) and the device-side contract are owlk_ring_advance's, per row. */
+int owlk_ring_advance_slots(long* state, long n_slots, long L, long max_rows, long cap, void* stream);
 /* MMDiT decode form (mmattn.py:46-86): the joint frames [n0 video | n1 audio] read straight from the
  * two modalities' qkv GEMM outputs (joint row r of frame f of batch b: video row (b nf + f) n0 + r for
  * r < n0, else audio row (b nf + f) n1 + r - n0), table row tab_off + f (n0 + n1) + r.  q goes to a
@@ -263,6 +287,18 @@ int owlk_attn_decode_ring_fwd(const void* q, long ldq, long sqb, const void* kbu
                               const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse, long B,
                               int H, long Lq, int head_dim, float scale, float score_bound, const long* state,
                               long Lnew, long window_tokens, long cap, void* stream);
+/* Slot form of owlk_attn_decode_ring_fwd for many sessions in one batch (the reference's
+ * inference/causvid_pipeline.py:112-163 per session, on the attn.py:83-107 cache branch; see
+ * owlk_qk_rope_fwd_kv_ring_slots for the state rows): its arguments with n_slots after state, state
+ * [n_slots, 4] = {start, cached tokens, rope offset, live} per row, batch row b on row b mod n_slots; B a
+ * multiple of n_slots and lse non-null (else returns 1).  Live slot: the single-state kernel's body, tile
+ * decomposition and bits on that slot's rows (outside the contract: its NaN o rows and lse, nothing read).
+ * Idle slot: nothing read, zero o rows, lse -inf. */
+int owlk_attn_decode_ring_slots_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                    const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
+                                    long B, int H, long Lq, int head_dim, float scale, float score_bound,
+                                    const long* state, long n_slots, long Lnew, long window_tokens, long cap,
+                                    void* stream);
 /* Joint-frame decode attention (mmattn.py:46-86, one new MMDiT frame against the cache): per (batch,
  * head) the n0 + n1 <= 80 query rows of q [B, n0 + n1, H D] (row stride ldq, batch stride sqb),
  * unmasked over Lkv key rows k / v (pointer + strides: [cache | new], or its last window rows for a

@@ -759,9 +759,33 @@ struct DecCfg {
 // lives at physical row (start + i) mod cap.  The tile decomposition stays the logical one (tile
 // w + 4 i of wave w from the first visible key), only each DMA row's source address wraps, so the
 // result equals the linear kernel's on an unrolled copy of the buffers bit for bit.
-template <int D, bool RING = false>
+// SLOTS... (owlk_attn_decode_ring_slots_fwd, one trailing long n_slots): state is [n_slots, 4] rows {start,
+// cached, offset, live} and batch blockIdx.z follows row blockIdx.z mod n_slots.  A live slot's workgroups run
+// the ring statements below on that row (out of contract: its NaN rows, nothing read); an idle slot's read
+// nothing and write zero o rows and lse -inf.  A parameter pack, so the single-state instantiations keep their
+// argument list and their code.
+template <int D, bool RING = false, typename... SLOTS>
 __global__ __launch_bounds__(256, 1) void attn_fwd16_split_k(FwdP p, const long* __restrict__ state, long Lnew,
-                                                             long wtok, long cap) {
+                                                             long wtok, long cap, SLOTS... n_slots) {
+  if constexpr (sizeof...(SLOTS) > 0) {
+    static_assert(RING, "the slot form is a ring form");
+    // the slot's row in ONE uniform 32-byte load (a vector type, so the position is not fetched in a second
+    // round trip behind the live flag), read from registers from here on
+    typedef long row_t __attribute__((ext_vector_type(4)));
+    const row_t row = *(const row_t*)(state + ((unsigned)blockIdx.z % (unsigned)(n_slots, ...)) * 4);
+    const long slot[4] = {row[0], row[1], row[2], row[3]};
+    state = slot;
+    if (state[3] == 0) {
+      constexpr int DQ = D / 4;
+      const int q = threadIdx.x >> 2, d0 = DQ * (threadIdx.x & 3);
+      if (q >= p.Lq) return;
+      bf16* O = p.o + blockIdx.z * p.sob + (long)q * p.ldo + blockIdx.y * D + d0;
+#pragma unroll
+      for (int h8 = 0; h8 < DQ / 8; ++h8) *(bf16x8*)(O + 8 * h8) = bf16x8{};
+      if ((threadIdx.x & 3) == 0 && p.lse) p.lse[((long)blockIdx.z * p.H + blockIdx.y) * p.Lq + q] = -INFINITY;
+      return;
+    }
+  }
   // device-resident cache state (owlk_attn_decode_fwd): {start, cached tokens, rope offset} of the
   // cache buffers p.k / p.v, so one captured HIP graph serves every frame of a growing cache; the
   // keys are [cache | the Lnew new rows], the last wtok of them for a windowed layer (wtok > 0)
@@ -1339,7 +1363,7 @@ extern "C" int owlk_attn_fwd(const void* q, long ldq, long sqb, const void* k, l
 static int attn_decode_launch(bool ring, const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
                               const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse, long B,
                               int H, long Lq, int head_dim, float scale, float score_bound, const long* state,
-                              long Lnew, long window_tokens, long cap, void* stream) {
+                              long Lnew, long window_tokens, long cap, void* stream, long n_slots = 0) {
   OWLK_REQUIRE(head_dim == 64 || head_dim == 128, "attn_decode_fwd: head_dim %d not built (64, 128)", head_dim);
   OWLK_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lq <= 64 && Lnew > 0 && state, "attn_decode_fwd: bad sizes");
   OWLK_REQUIRE(cap >= Lnew, "attn_decode_fwd: cache capacity %ld rows", cap);
@@ -1356,7 +1380,13 @@ static int attn_decode_launch(bool ring, const void* q, long ldq, long sqb, cons
   p.bound = score_bound;
   p.m = owlk_make_mask(1, 0, 0, 0, 1, nullptr, nullptr, nullptr, nullptr, 0);
   const dim3 grid(1, (unsigned)H, (unsigned)B);
-  if (ring && head_dim == 64)
+  if (n_slots > 0 && head_dim == 64)  // one state row per slot (owlk_attn_decode_ring_slots_fwd)
+    hipLaunchKernelGGL((attn_fwd16_split_k<64, true, long>), grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
+                       window_tokens, cap, n_slots);
+  else if (n_slots > 0)
+    hipLaunchKernelGGL((attn_fwd16_split_k<128, true, long>), grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
+                       window_tokens, cap, n_slots);
+  else if (ring && head_dim == 64)
     hipLaunchKernelGGL((attn_fwd16_split_k<64, true>), grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
                        window_tokens, cap);
   else if (ring)
@@ -1368,7 +1398,9 @@ static int attn_decode_launch(bool ring, const void* q, long ldq, long sqb, cons
   else
     hipLaunchKernelGGL(attn_fwd16_split_k<128>, grid, dim3(256), 0, (hipStream_t)stream, p, state, Lnew,
                        window_tokens, cap);
-  return owlk::check_launch(ring ? "attn_decode_ring_fwd" : "attn_decode_fwd");
+  return owlk::check_launch(n_slots > 0 ? "attn_decode_ring_slots_fwd"
+                            : ring      ? "attn_decode_ring_fwd"
+                                        : "attn_decode_fwd");
 }
 
 extern "C" int owlk_attn_decode_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
@@ -1390,6 +1422,23 @@ extern "C" int owlk_attn_decode_ring_fwd(const void* q, long ldq, long sqb, cons
                                          long cap, void* stream) {
   return attn_decode_launch(true, q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o, ldo, sob, lse, B, H, Lq, head_dim,
                             scale, score_bound, state, Lnew, window_tokens, cap, stream);
+}
+
+// Slot form for many sessions in one batch (sampling/stream_pool.py; the reference's
+// inference/causvid_pipeline.py:112-163 serves one session per pipeline, on the attn.py:83-107 cache branch):
+// owlk_attn_decode_ring_fwd with one state row {start, cached, offset, live} per slot, batch row b on row
+// b mod n_slots (the CFG halves [cond | uncond] of a session share one).  A live slot's o and lse are the
+// single-state kernel's on that slot's rows and state; an idle slot reads nothing and gets zero o rows and
+// lse -inf; a live slot outside the contract gets NaN rows, nothing read.  No slot's state reaches another's.
+extern "C" int owlk_attn_decode_ring_slots_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                               long skb, const void* vbuf, long ldv, long svb, void* o, long ldo,
+                                               long sob, float* lse, long B, int H, long Lq, int head_dim,
+                                               float scale, float score_bound, const long* state, long n_slots,
+                                               long Lnew, long window_tokens, long cap, void* stream) {
+  OWLK_REQUIRE(lse && n_slots > 0 && B > 0 && B % n_slots == 0 && B <= 65535,
+               "attn_decode_ring_slots_fwd: lse required, B=%ld batch rows a multiple of n_slots=%ld", B, n_slots);
+  return attn_decode_launch(true, q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o, ldo, sob, lse, B, H, Lq, head_dim,
+                            scale, score_bound, state, Lnew, window_tokens, cap, stream, n_slots);
 }
 
 extern "C" int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, const void* k, long ldk, long skb,

@@ -402,13 +402,18 @@ __global__ __launch_bounds__(256) void qk_rope_fwd_k(const bf16* __restrict__ qk
 // KV cache's slots behind the cached window, so the decode step needs no separate cache copies
 // RING (owlk_qk_rope_fwd_kv_ring): the buffers are rings of cap rows, token t's k / v go to row
 // (start + cached + t) mod cap
-template <int D, bool RING = false>
+// SLOTS... (owlk_qk_rope_fwd_kv_ring_slots, one trailing long n_slots): state is [n_slots, 4] rows {start,
+// cached, offset, live} and batch bb follows row bb mod n_slots; an idle row (live = 0) gets zero q rows and
+// touches neither cache nor table.  A parameter pack, so the single-state instantiations keep their argument
+// list and their code; a live slot runs the same statements on its own state row.
+template <int D, bool RING = false, typename... SLOTS>
 __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv, long ldq, long T, long L, int H,
                                                     const float* __restrict__ cosb, const float* __restrict__ sinb,
                                                     long ld_tab, long tab_off, bf16* __restrict__ qo, long ldqo,
                                                     long sqo, bf16* __restrict__ ko, long ldko, long sko,
                                                     bf16* __restrict__ vo, long ldvo, long svo,
-                                                    const long* __restrict__ state, long n_tab, long cap) {
+                                                    const long* __restrict__ state, long n_tab, long cap,
+                                                    SLOTS... n_slots) {
   constexpr int CPR = D / 8;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long rowid = gid / CPR;  // (token, which, head)
@@ -417,6 +422,23 @@ __global__ __launch_bounds__(256) void qk_rope_kv_k(const bf16* __restrict__ qkv
   const long tok = rowid / (3 * H);
   const int wh = rowid % (3 * H);  // which * H + head
   const long bb = tok / L, t = tok - bb * L;
+  if constexpr (sizeof...(SLOTS) > 0) {
+    // the slot's row in ONE 32-byte load (a vector type, so the position is not fetched in a second round trip
+    // behind the live flag), read from registers from here on; the host bounds T / L by 2^31
+    typedef long row_t __attribute__((ext_vector_type(4)));
+    const row_t row = *(const row_t*)(state + ((unsigned)bb % (unsigned)(n_slots, ...)) * 4);
+    const long slot[4] = {row[0], row[1], row[2], row[3]};
+    state = slot;
+    if (state[3] == 0) {  // idle slot: zero q rows, nothing else read or written
+      if (wh < H) {
+        const bf16x4 z4 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+        bf16* o = qo + bb * sqo + t * ldqo + (long)wh * D;
+        *(bf16x4*)(o + j * 4) = z4;
+        *(bf16x4*)(o + D / 2 + j * 4) = z4;
+      }
+      return;
+    }
+  }
   if (state) {  // {start, cached tokens, rope offset}: k / v rows go behind the window of the buffers
     const long start = state[0], cached = state[1], off = state[2];
     if (start < 0 || cached < 0 || (RING ? start >= cap || cached + L > cap : start + cached + L > cap) || off < 0 ||
@@ -1067,6 +1089,32 @@ extern "C" int owlk_qk_rope_fwd_kv_ring(const void* qkv, long ldq, long T, long 
                            svb, state, cap, true, stream);
 }
 
+static int qk_rope_kv_slots_launch(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
+                                   const float* sinb, long ld_tab, long n_tab, const long* state, long n_slots,
+                                   void* qo, long ldqo, long sqo, void* ko, long ldko, long sko, void* vo, long ldvo,
+                                   long svo, long cap, void* stream);
+
+// Slot form for many sessions in one batch (sampling/stream_pool.py; the reference's
+// inference/causvid_pipeline.py:112-163 serves one session per pipeline, on the attn.py:83-107 cache branch):
+// owlk_qk_rope_fwd_kv_ring with one state row {start, cached, offset, live} per slot, batch row b on row
+// b mod n_slots (the CFG halves [cond | uncond] of a session share one).  A live slot's rows are the
+// single-state kernel's; an idle one gets zero q rows; one outside the contract NaN q rows; neither touches
+// the cache or the table, and no slot's state reaches another's rows.
+extern "C" int owlk_qk_rope_fwd_kv_ring_slots(const void* qkv, long ldq, long T, long L, int H, int D,
+                                              const float* cosb, const float* sinb, long ld_tab, long n_tab,
+                                              const long* state, long n_slots, void* qo, long ldqo, long sqo,
+                                              void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb,
+                                              long cap, void* stream) {
+  OWLK_REQUIRE(state, "qk_rope_fwd_kv_ring_slots: state pointer required");
+  OWLK_REQUIRE(n_tab > 0 && cap > 0, "qk_rope_fwd_kv_ring_slots: rope table rows / cache capacity required");
+  OWLK_REQUIRE(L > 0 && T > 0 && T % L == 0 && T / L < (1L << 31) && n_slots > 0 && (T / L) % n_slots == 0,
+               "qk_rope_fwd_kv_ring_slots: T=%ld must be a whole number of L=%ld rows for a multiple of n_slots=%ld "
+               "batch rows",
+               T, L, n_slots);
+  return qk_rope_kv_slots_launch(qkv, ldq, T, L, H, D, cosb, sinb, ld_tab, n_tab, state, n_slots, qo, ldqo, sqo, kbuf,
+                                 ldk, skb, vbuf, ldv, svb, cap, stream);
+}
+
 // RoPE rebase between streamed frames (causvid_pipeline.py keeps generating past the rope.py:40-49 table;
 // MotionRoPE / Audio1DRoPE angles, rope.py:82-179, are linear in the frame index, so q.k depends only on
 // frame differences): the `rows` live logical rows of the ring K buffer kbuf [B, cap, H D], from
@@ -1103,8 +1151,7 @@ extern "C" int owlk_rope_rebase(void* kbuf, long ldk, long skb, long B, int H, i
 // (causvid_pipeline.py's sliding window).  A state outside the contract is not followed: cached becomes
 // -1, which every ring kernel treats as out of contract (NaN rows, nothing read or written), and it
 // stays -1 under further advances.
-__global__ void ring_advance_k(long* __restrict__ state, long L, long max_rows, long cap) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+__device__ __forceinline__ void ring_advance_row(long* __restrict__ state, long L, long max_rows, long cap) {
   const long start = state[0], cached = state[1], off = state[2];
   // cached <= cap - L first, so cached + L cannot overflow; offset + L must not either
   if (start < 0 || start >= cap || cached < 0 || cached > cap - L || off < 0 || off > INT64_MAX - L) {
@@ -1122,6 +1169,21 @@ __global__ void ring_advance_k(long* __restrict__ state, long L, long max_rows, 
   state[2] = off + L;
 }
 
+__global__ void ring_advance_k(long* __restrict__ state, long L, long max_rows, long cap) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  ring_advance_row(state, L, max_rows, cap);
+}
+
+// Slot form (owlk_ring_advance_slots): thread s applies the rule to row s of state [n_slots, 4] where its
+// live flag is set and leaves an idle row alone; a row outside the contract gets cached = -1, no other
+// row does.  Each thread reads and writes its own row only.
+__global__ __launch_bounds__(64) void ring_advance_slots_k(long* __restrict__ state, long n_slots, long L,
+                                                           long max_rows, long cap) {
+  const long s = (long)blockIdx.x * 64 + threadIdx.x;
+  if (s >= n_slots || state[4 * s + 3] == 0) return;
+  ring_advance_row(state + 4 * s, L, max_rows, cap);
+}
+
 // The streamed frame's commit + eviction on the device, so that a whole frame -- Euler steps, re-noise,
 // the forward that writes the finished frame's rows, this -- is one captured graph
 // (sampling/stream.py graphed="frame"; the reference's inference/causvid_pipeline.py:112-163 does the
@@ -1134,6 +1196,41 @@ extern "C" int owlk_ring_advance(long* state, long L, long max_rows, long cap, v
                max_rows, cap);
   hipLaunchKernelGGL(ring_advance_k, dim3(1), dim3(1), 0, (hipStream_t)stream, state, L, max_rows, cap);
   return owlk::check_launch("ring_advance");
+}
+
+// The same for a pool of sessions (sampling/stream_pool.py; causvid_pipeline.py:112-163 per session): every
+// live row of state [n_slots, 4] {start, cached, offset, live} takes the rule in one launch, so one captured
+// tick serves sessions that were opened, wrapped and rebased at different times.
+extern "C" int owlk_ring_advance_slots(long* state, long n_slots, long L, long max_rows, long cap, void* stream) {
+  OWLK_REQUIRE(state, "ring_advance_slots: state pointer required");
+  OWLK_REQUIRE(n_slots > 0 && n_slots <= (1L << 20), "ring_advance_slots: n_slots=%ld out of range", n_slots);
+  OWLK_REQUIRE(L > 0 && max_rows > 0 && cap > 0 && max_rows <= cap - L,
+               "ring_advance_slots: need L > 0, 0 < max_rows and max_rows + L <= cap (L=%ld max_rows=%ld cap=%ld)", L,
+               max_rows, cap);
+  hipLaunchKernelGGL(ring_advance_slots_k, dim3((unsigned)((n_slots + 63) / 64)), dim3(64), 0, (hipStream_t)stream,
+                     state, n_slots, L, max_rows, cap);
+  return owlk::check_launch("ring_advance_slots");
+}
+
+static int qk_rope_kv_slots_launch(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,
+                                   const float* sinb, long ld_tab, long n_tab, const long* state, long n_slots,
+                                   void* qo, long ldqo, long sqo, void* ko, long ldko, long sko, void* vo, long ldvo,
+                                   long svo, long cap, void* stream) {
+  OWLK_REQUIRE(D == 64 || D == 128, "qk_rope_fwd_kv_ring_slots: head_dim %d unsupported", D);
+  OWLK_REQUIRE(((uintptr_t)qo | (uintptr_t)ko | (uintptr_t)vo) % 16 == 0 && ldqo % 8 == 0 && ldko % 8 == 0 &&
+                   ldvo % 8 == 0 && sqo % 8 == 0 && sko % 8 == 0 && svo % 8 == 0,
+               "qk_rope_fwd_kv_ring_slots: destinations must be 16-byte aligned");
+  const long threads = T * 3 * H * (D / 8);
+  dim3 g((unsigned)((threads + 255) / 256));
+  if (D == 64)
+    hipLaunchKernelGGL((qk_rope_kv_k<64, true, long>), g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, ldq, T,
+                       L, H, cosb, sinb, ld_tab, 0L, (bf16*)qo, ldqo, sqo, (bf16*)ko, ldko, sko, (bf16*)vo, ldvo, svo,
+                       state, n_tab, cap, n_slots);
+  else
+    hipLaunchKernelGGL((qk_rope_kv_k<128, true, long>), g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv, ldq,
+                       T, L, H, cosb, sinb, ld_tab, 0L, (bf16*)qo, ldqo, sqo, (bf16*)ko, ldko, sko, (bf16*)vo, ldvo,
+                       svo, state, n_tab, cap, n_slots);
+  return owlk::check_launch("qk_rope_fwd_kv_ring_slots");
 }
 
 static int qk_rope_kv_launch(const void* qkv, long ldq, long T, long L, int H, int D, const float* cosb,

@@ -38,6 +38,9 @@ _SIGS = {
     "owlk_attn_decode_ring_fwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, L, I, L, I, F, F, P, L, L, L, P],
     "owlk_rope_rebase": [P, L, L, L, I, I, L, L, L, P, P, L, L, L, L, P],
     "owlk_ring_advance": [P, L, L, L, P],
+    "owlk_qk_rope_fwd_kv_ring_slots": [P, L, L, L, I, I, P, P, L, L, P, L, P, L, L, P, L, L, P, L, L, L, P],
+    "owlk_attn_decode_ring_slots_fwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, L, I, L, I, F, F, P, L, L, L, L, P],
+    "owlk_ring_advance_slots": [P, L, L, L, L, P],
     "owlk_mm_qk_rope_fwd_kv": [P, L, P, L, L, L, I, I, I, I, P, P, L, L, L, P, L, L, P, L, L, P, L, L, P],
     "owlk_attn_decode_joint_fwd": [P, L, L, P, L, L, P, L, L, P, L, P, L, P, L, I, I, I, L, I, F, F, P],
     "owlk_mm_qk_rope_fwd_kv_ring": [P, L, P, L, L, L, I, I, I, I, P, P, L, L, P, P, L, L, P, L, L, P, L, L, L, P],

@@ -402,6 +402,50 @@ def ring_advance(state, L, max_rows, cap):
     call("owlk_ring_advance", ptr(state), int(L), int(max_rows), int(cap), stream())
 
 
+def _slot_state(state, B):
+    """state [n_slots, 4] int64 {start, cached, offset, live} for B batch rows (row b on state row b mod n_slots)"""
+    assert state.dtype == torch.int64 and state.dim() == 2 and state.shape[1] == 4 and state.is_cuda and \
+        state.is_contiguous(), "slot state: a contiguous int64 device array [n_slots, 4]"
+    assert B % state.shape[0] == 0, f"{B} batch rows are not a multiple of {state.shape[0]} slots"
+    return state.shape[0]
+
+
+def qk_rope_fwd_kv_ring_slots(qkv, B, L, H, D, cos, sin, state, q_out, kbuf, vbuf):
+    """qk_rope_fwd_kv_ring with one state row per slot (state [n_slots, 4] {start, cached, offset, live},
+    batch row b on row b mod n_slots): a live slot's rows as the single-state kernel writes them, an idle
+    slot's q rows zero and its cache rows untouched, a slot outside the contract NaN q rows."""
+    n_slots = _slot_state(state, B)
+    assert q_out.shape == (B, L, H * D) and q_out.stride(2) == 1
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    call("owlk_qk_rope_fwd_kv_ring_slots", ptr(qkv), qkv.stride(0), B * L, L, H, D, ptr(cos), ptr(sin), cos.stride(0),
+         cos.shape[0], ptr(state), n_slots, ptr(q_out), q_out.stride(1), q_out.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), kbuf.shape[1], stream())
+
+
+def attn_decode_ring_slots_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0, scale=None, score_bound=0.0):
+    """attn_decode_ring_fwd with one state row per slot (see qk_rope_fwd_kv_ring_slots): a live slot's o and
+    lse are the single-state kernel's, an idle slot's o rows zero and lse -inf with nothing read."""
+    B, Lq, _ = q.shape
+    assert decode_dev_supported(D, Lq), f"attn_decode_ring_slots_fwd: head_dim {D} / {Lq} query rows not supported"
+    n_slots = _slot_state(state, B)
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    o = torch.empty_like(q)
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32)
+    call("owlk_attn_decode_ring_slots_fwd", ptr(q), q.stride(1), q.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), ptr(o), o.stride(1), o.stride(0), ptr(lse), B, H, Lq,
+         D, float(scale if scale is not None else D ** -0.5), float(score_bound), ptr(state), n_slots, Lnew,
+         window_tokens, kbuf.shape[1], stream())
+    return o, lse
+
+
+def ring_advance_slots(state, L, max_rows, cap):
+    """ring_advance on every live row of state [n_slots, 4] {start, cached, offset, live} in one launch; an
+    idle row stays as it is, a row outside the contract gets cached = -1."""
+    assert state.dtype == torch.int64 and state.dim() == 2 and state.shape[1] == 4 and state.is_cuda and \
+        state.is_contiguous()
+    call("owlk_ring_advance_slots", ptr(state), state.shape[0], int(L), int(max_rows), int(cap), stream())
+
+
 def mm_qk_rope_fwd_kv(qkv0, qkv1, B, nf, n0, n1, H, D, cos, sin, tab_off, q_out, k_out, v_out):
     """MMDiT decode form: the two modalities' qkv GEMM outputs (qkv0 [B nf n0, 3 H D] video, qkv1
     [B nf n1, 3 H D] audio) -> rotated q of the joint frames [n0 video | n1 audio] into q_out

@@ -372,3 +372,141 @@ class RingKVCache(SingleKVCache):
 
     def clone(self):
         raise RuntimeError("RingKVCache keeps fixed buffers; clone is not supported")
+
+
+class SlotRingKVCache:
+    """Many sessions in one batch (sampling/stream_pool.py StreamPool): per layer K/V rings
+    ``[batch_rows, capacity, d]`` allocated once, ``batch_rows`` = n_slots, or 2 n_slots with CFG
+    ([cond | uncond]: batch row b belongs to slot ``b % n_slots``), and ONE device state ``[n_slots, 4]``, row s
+    = {start, cached tokens, rope offset, live}, which the slot forms of the ring kernels read
+    (``owlk_qk_rope_fwd_kv_ring_slots``, ``owlk_attn_decode_ring_slots_fwd``) and ``owlk_ring_advance_slots``
+    moves.  Every layer of a slot advances together, so the host keeps one exact mirror per slot (start, len,
+    offsets, live).  Decode only: a slot's context is cached through ``slot_view`` (a RingKVCache over that
+    slot's batch rows), a streamed frame is committed by ``advance``; idle slots cost no cache traffic."""
+
+    ring = True
+    should_update = False  # frames are committed by advance(), not by the forward's bookkeeping
+    noise_caches = 0.0
+
+    def __init__(self, config, capacity, n_slots, batch_rows, rope=None, device="cuda", dtype=torch.bfloat16):
+        assert capacity > 0 and n_slots > 0 and batch_rows in (n_slots, 2 * n_slots)
+        self.config = config
+        self.capacity = int(capacity)
+        self.n_slots = int(n_slots)
+        self.rope = rope
+        d = config.d_model
+        self.bufs = [tuple(torch.empty(batch_rows, self.capacity, d, device=device, dtype=dtype) for _ in range(2))
+                     for _ in range(config.n_layers)]
+        self.dev = torch.zeros(self.n_slots, 4, dtype=torch.int64, device=device)
+        self.start = [0] * self.n_slots
+        self.len = [0] * self.n_slots
+        self.offsets = [0] * self.n_slots
+        self.live = [False] * self.n_slots
+
+    # ------------------------------------------------------------------ slots
+    def free_slot(self):
+        """the lowest idle slot, or None when every slot is live"""
+        return next((s for s in range(self.n_slots) if not self.live[s]), None)
+
+    def live_slots(self):
+        return [s for s in range(self.n_slots) if self.live[s]]
+
+    def slot_view(self, slot):
+        """A RingKVCache over the slot's batch rows ``bufs[slot::n_slots]`` (strided views, nothing allocated)
+        for that session's context pass: the forward's ``update`` writes rows 0.. of the slot's rings."""
+        view = RingKVCache(self.config, self.capacity, rope=self.rope)
+        view.reset(self.bufs[0][0].shape[0] // self.n_slots)
+        view.bufs = [(kb[slot::self.n_slots], vb[slot::self.n_slots]) for kb, vb in self.bufs]
+        return view
+
+    def _sync_slot(self, slot):
+        """the slot's mirror -> its device row (outside graph capture: a small host-to-device copy)"""
+        s, n, o = self.start[slot], self.len[slot], self.offsets[slot]
+        assert 0 <= s < self.capacity and 0 <= n <= self.capacity and o >= 0
+        self.dev[slot].copy_(torch.tensor([s, n, o, int(self.live[slot])], dtype=torch.int64))
+
+    def open_slot(self, slot, rows):
+        """the slot goes live with `rows` context rows cached from physical row 0 at positions 0 .. rows - 1"""
+        assert not self.live[slot], f"slot {slot} is live"
+        assert 0 < rows <= self.capacity
+        self.start[slot], self.len[slot], self.offsets[slot], self.live[slot] = 0, int(rows), int(rows), True
+        self._sync_slot(slot)
+
+    def close_slot(self, slot):
+        """the slot goes idle on host and device; its rows stay where they are and are never read again (a
+        later open_slot starts a new window)"""
+        assert self.live[slot], f"slot {slot} is idle"
+        self.start[slot], self.len[slot], self.offsets[slot], self.live[slot] = 0, 0, 0, False
+        self._sync_slot(slot)
+
+    # ------------------------------------------------------------------ what the DiT's cached forward reads
+    def get_offset(self, idx=0):
+        """the largest rope offset among the live slots (0 with none): the one an eager forward's table check
+        has to hold for, since every live slot's offset is at most this"""
+        return max((self.offsets[s] for s in self.live_slots()), default=0)
+
+    def length_at(self, idx=0):
+        return max((self.len[s] for s in self.live_slots()), default=0)
+
+    def commit_device(self, layer_ind, L):
+        raise RuntimeError("SlotRingKVCache: frames are committed by advance(), once for every layer and slot")
+
+    def enable_cache_updates(self):
+        raise RuntimeError("SlotRingKVCache: cache a slot's context through slot_view(slot)")
+
+    def advance(self, L, max_rows, device=True):
+        """RingKVCache.advance's rule on every live slot:
+
+            len += L; offsets += L;  then, if len > max_rows:  start = (start + L) % capacity; len -= L
+
+        device=True: one ``owlk_ring_advance_slots`` launch moves the device rows (under graph capture only
+        the launch is recorded and the mirror stays; the caller advances it once per replay with
+        device=False)."""
+        L, max_rows = int(L), int(max_rows)
+        assert L > 0 and 0 < max_rows and max_rows + L <= self.capacity, \
+            f"advance: need 0 < L, 0 < max_rows and max_rows + L <= capacity ({L}, {max_rows}, {self.capacity})"
+        if device:
+            from .. import kernels as K
+            K.ring_advance_slots(self.dev, L, max_rows, self.capacity)
+            if torch.cuda.is_current_stream_capturing():
+                return
+        for s in self.live_slots():
+            assert self.len[s] + L <= self.capacity, "ring capacity exceeded (evict before committing)"
+            self.len[s] += L
+            self.offsets[s] += L
+            if self.len[s] > max_rows:
+                self.start[s] = (self.start[s] + L) % self.capacity
+                self.len[s] -= L
+
+    def host_state(self):
+        """the mirror as device_state() returns the device rows"""
+        return [(self.start[s], self.len[s], self.offsets[s], int(self.live[s])) for s in range(self.n_slots)]
+
+    def device_state(self):
+        """every row (start, cached, offset, live) read back from the device (a synchronising copy)"""
+        return [tuple(r) for r in self.dev.tolist()]
+
+    def rebase(self, slot, shift_tokens, rope=None):
+        """RingKVCache.rebase for one slot: its cached K rows (the slot's batch rows of every layer) are
+        re-rotated in place to positions lower by `shift_tokens` (``owlk_rope_rebase`` with the slot view's
+        batch stride), then its offset drops and its device row is rewritten.  Other slots are untouched."""
+        from .. import kernels as K
+        rope = rope if rope is not None else self.rope
+        assert rope is not None, "rebase needs the model's RoPE tables"
+        assert self.live[slot], f"slot {slot} is idle"
+        tpf = self.config.tokens_per_frame
+        assert shift_tokens >= 0 and shift_tokens % tpf == 0, "rebase by whole frames"
+        if shift_tokens == 0:
+            return
+        H = self.config.n_heads
+        D = self.config.d_model // H
+        old = self.offsets[slot] - self.len[slot]
+        if old < shift_tokens:
+            raise RuntimeError(f"rebase by {shift_tokens} tokens would move slot {slot}'s oldest cached key (position "
+                               f"{old}) below 0")
+        if self.len[slot]:
+            for kb, _ in self.bufs:
+                K.rope_rebase(kb[slot::self.n_slots], H, D, self.start[slot], self.len[slot], rope.cos, rope.sin, old,
+                              old - shift_tokens)
+        self.offsets[slot] -= shift_tokens
+        self._sync_slot(slot)

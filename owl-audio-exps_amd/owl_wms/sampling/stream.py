@@ -233,14 +233,20 @@ class _RingStream:
         is an ordinary decode forward and `advance` stands for commit_device + sync_device_state +
         truncate.  Eager it also advances the host mirror; captured it executes nothing and the mirror
         stays (RingKVCache.advance)."""
-        n, tpf = len(self._like), self.core.config.tokens_per_frame
+        n = len(self._like)
         xs, t = tuple(s[f"x{i}"] for i in range(n)), s["t"]
         own = {"t"} | {f"{c}{i}" for c in "xz" for i in range(n)}
         ctrl = {k: v for k, v in s.items() if k not in own}  # what _controls returned
         for t_idx in range(self.n_steps):
             xs, t = self._euler_step(xs, t, ctrl, self._dt[t_idx])
+        return self._commit_frame(xs, t, tuple(s[f"z{i}"] for i in range(n)), ctrl)
+
+    def _commit_frame(self, xs, t, zs, ctrl):
+        """_frame after its Euler steps: the finished frame copied out, the re-noise with the draws zs, the
+        forward on the re-noised frame, the ring position's advance on the device."""
+        tpf = self.core.config.tokens_per_frame
         frame = tuple(x.clone() for x in xs)
-        noisy = tuple(renoise(x, s[f"z{i}"], self.noise_prev) for i, x in enumerate(xs))
+        noisy = tuple(renoise(x, z, self.noise_prev) for x, z in zip(xs, zs))
         t_noisy = torch.ones_like(t) * self.noise_prev
         self._forward(self.kv_cache, noisy, t_noisy, ctrl.get("mouse"), ctrl.get("btn"))
         self.kv_cache.advance(tpf, self.max_cached_frames * tpf)
