@@ -235,6 +235,18 @@ int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const void* qkv1, lo
                                 int n1, int H, int D, const float* cosb, const float* sinb, long ld_tab, long n_tab,
                                 const long* state, void* qo, long ldqo, long sqo, void* kbuf, long ldk, long skb,
                                 void* vbuf, long ldv, long svb, long cap, void* stream);
+/* Slot form of owlk_mm_qk_rope_fwd_kv_ring for many audio + video sessions in one batch (sampling/stream_pool.py
+ * AVStreamPool; the reference's inference/causvid_pipeline.py:112-163 serves one session per pipeline, on the
+ * mmattn.py:46-86 cache branch): its arguments with n_slots after state.  state [n_slots, 4] = {start, cached
+ * tokens, rope offset, live} per row, batch row b on row b mod n_slots, with the per-slot semantics stated above
+ * owlk_qk_rope_fwd_kv_ring_slots: a live slot's q, k, v rows are the single-state entry's on that slot's batch rows;
+ * an idle slot gets zero q rows and one outside the contract NaN q rows, and neither touches the cache or the table.
+ * B a multiple of n_slots (else returns 1); head_dim 64 or 128. */
+int owlk_mm_qk_rope_fwd_kv_ring_slots(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf, int n0,
+                                      int n1, int H, int D, const float* cosb, const float* sinb, long ld_tab,
+                                      long n_tab, const long* state, long n_slots, void* qo, long ldqo, long sqo,
+                                      void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
+                                      void* stream);
 int owlk_qk_rope_bwd(const void* dqk, long ldd, const void* qkv, long ldq, long T, int H, int D,
                      const float* cosb, const float* sinb, long ld_tab, long n_tab, long tab_off, long tpos_div,
                      const float* rstd, void* dqkv, long ldg, void* stream);
@@ -323,6 +335,19 @@ int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb, const voi
                                     float* lse, long B, int H, int n0, int n1, int head_dim, float scale,
                                     float score_bound, const long* state, long window_tokens, long cap,
                                     void* stream);
+/* Slot form of owlk_attn_decode_joint_ring_fwd for many audio + video sessions in one batch
+ * (sampling/stream_pool.py AVStreamPool; the reference's inference/causvid_pipeline.py:112-163 per session, on the
+ * mmattn.py:46-86 cache branch; see owlk_qk_rope_fwd_kv_ring_slots for the state rows): its arguments with n_slots
+ * after state, batch row b on row b mod n_slots; lse non-null, B a multiple of n_slots and <= 65535 (else returns 1);
+ * head_dim 64, n0 + n1 <= 80.  Each workgroup takes its key range from its slot's row, so the slots of one launch
+ * have different key counts.  Live slot: the single-state kernel's body, tile decomposition and bits on that slot's
+ * rows (outside the contract: its NaN o0 / o1 rows and lse, nothing read).  Idle slot: nothing read, zero rows, lse
+ * -inf. */
+int owlk_attn_decode_joint_ring_slots_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                          const void* vbuf, long ldv, long svb, void* o0, long ldo0, void* o1,
+                                          long ldo1, float* lse, long B, int H, int n0, int n1, int head_dim,
+                                          float scale, float score_bound, const long* state, long n_slots,
+                                          long window_tokens, long cap, void* stream);
 /* Wide ring decode for streaming the dit-backbone audio + video core (the reference's
  * inference/causvid_pipeline.py on configs/causvid.yml: a 65-row joint frame [64 video | 1 audio] through the
  * plain DiT, attn.py:86-107 cache branch): owlk_attn_decode_ring_fwd's arguments with one frame of
@@ -337,6 +362,16 @@ int owlk_attn_decode_wide_ring_fwd(const void* q, long ldq, long sqb, const void
                                    const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
                                    long B, int H, long Lq, int head_dim, float scale, float score_bound,
                                    const long* state, long Lnew, long window_tokens, long cap, void* stream);
+/* Slot form of owlk_attn_decode_wide_ring_fwd for many sessions of the dit-backbone audio + video core in one batch
+ * (sampling/stream_pool.py AVDiTStreamPool; the reference's inference/causvid_pipeline.py:112-163 per session, a
+ * 65-row joint frame through the attn.py:86-107 cache branch): its arguments with n_slots after state, the B and lse
+ * conditions and the per-slot semantics of owlk_attn_decode_joint_ring_slots_fwd; head_dim 64, 0 < Lq <= 80.  o and
+ * lse equal that entry's o0 | o1 and lse on the same buffers and state rows. */
+int owlk_attn_decode_wide_ring_slots_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                         const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
+                                         long B, int H, long Lq, int head_dim, float scale, float score_bound,
+                                         const long* state, long n_slots, long Lnew, long window_tokens, long cap,
+                                         void* stream);
 /* delta[b, h, t] = sum_d dO * O (fp32), the backward's row constant */
 int owlk_attn_delta(const void* o, const void* dout, long ld, long B, long L, int H, int D, float* delta,
                     void* stream);

@@ -1046,11 +1046,40 @@ __device__ __forceinline__ bf16* joint_out_row(const P& p, long b, int q) {
     return q < p.n0 ? p.o0 + (b * p.n0 + q) * p.ldo0 : p.o1 + (b * p.n1 + (q - p.n0)) * p.ldo1;
 }
 
-template <bool RING = false, bool WIDE = false>
-__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING, WIDE> p) {
+// SLOTS... (owlk_attn_decode_joint_ring_slots_fwd / owlk_attn_decode_wide_ring_slots_fwd, one trailing long
+// n_slots): p.state is [n_slots, 4] rows {start, cached, offset, live} and batch blockIdx.z follows row
+// blockIdx.z mod n_slots, as in attn_fwd16_split_k's slot form.  The row is loaded once, uniformly, and the ring
+// statements below run on it, so org, Lkv and the tile count stay scalar and differ from slot to slot within one
+// launch.  An idle slot's workgroups return before any LDS or DMA traffic with zero rows and lse -inf over the
+// rows the NaN path covers.  A parameter pack, so the single-state instantiations keep their argument list and
+// their code.
+template <bool RING = false, bool WIDE = false, typename... SLOTS>
+__global__ __launch_bounds__(256, 1) void attn_decode_joint_k(JointArg<RING, WIDE> p, SLOTS... n_slots) {
   static_assert(RING || !WIDE, "the wide output comes in the ring form only");
   using C = DecCfg<64>;
   constexpr int D = 64, KTD = C::KTD, NQT = JointCfg::NQT, QR = JointCfg::QR;
+  [[maybe_unused]] long slot[4];  // the slot form's state row, alive for the whole body
+  if constexpr (sizeof...(SLOTS) > 0) {
+    static_assert(RING, "the slot form is a ring form");
+    typedef long row_t __attribute__((ext_vector_type(4)));
+    const row_t row = *(const row_t*)(p.state + ((unsigned)blockIdx.z % (unsigned)(n_slots, ...)) * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) slot[e] = row[e];
+    p.state = slot;
+    if (slot[3] == 0) {
+      const long b = blockIdx.z;
+      const int head = blockIdx.y;
+      for (int item = threadIdx.x; item < 4 * QR; item += 256) {
+        const int q = item >> 2, d0 = 16 * (item & 3);
+        if (q >= p.Lq) continue;
+        bf16* O = joint_out_row<WIDE>(p, b, q) + head * D + d0;
+        *(bf16x8*)O = bf16x8{};
+        *(bf16x8*)(O + 8) = bf16x8{};
+        if ((item & 3) == 0) p.lse[(b * p.H + head) * p.Lq + q] = -INFINITY;
+      }
+      return;
+    }
+  }
   long org = 0, cap = 0;
   if constexpr (RING) {
     cap = p.cap;
@@ -1476,11 +1505,11 @@ extern "C" int owlk_attn_decode_joint_fwd(const void* q, long ldq, long sqb, con
 // of them; logical key i of the visible range lives at physical row (start + first + i) mod cap.  The
 // same bits as the linear entry on an unrolled copy of the buffers.  Contract: 0 <= start < cap,
 // cached >= 0, total <= cap; outside it NaN o0 / o1 rows and lse, nothing read.
-extern "C" int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
-                                               long skb, const void* vbuf, long ldv, long svb, void* o0, long ldo0,
-                                               void* o1, long ldo1, float* lse, long B, int H, int n0, int n1,
-                                               int head_dim, float scale, float score_bound, const long* state,
-                                               long window_tokens, long cap, void* stream) {
+static int attn_decode_joint_ring_launch(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                         const void* vbuf, long ldv, long svb, void* o0, long ldo0, void* o1,
+                                         long ldo1, float* lse, long B, int H, int n0, int n1, int head_dim,
+                                         float scale, float score_bound, const long* state, long window_tokens,
+                                         long cap, void* stream, long n_slots = 0) {
   OWLK_REQUIRE(head_dim == 64, "attn_decode_joint_ring_fwd: head_dim %d not built (64)", head_dim);
   OWLK_REQUIRE(B > 0 && H > 0 && n0 > 0 && n1 > 0 && B <= 65535 && H <= 65535 && state && window_tokens >= 0,
                "attn_decode_joint_ring_fwd: bad sizes");
@@ -1503,9 +1532,41 @@ extern "C" int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb
   p.ldq = ldq; p.sqb = sqb; p.ldk = ldk; p.skb = skb; p.ldv = ldv; p.svb = svb; p.ldo0 = ldo0; p.ldo1 = ldo1;
   p.Lq = (long)n0 + n1; p.Lkv = 0; p.n0 = n0; p.n1 = n1; p.H = H;  // Lkv from the device state
   p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL(attn_decode_joint_k<true>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0, (hipStream_t)stream,
-                     p);
-  return owlk::check_launch("attn_decode_joint_ring_fwd");
+  if (n_slots > 0)  // one state row per slot (owlk_attn_decode_joint_ring_slots_fwd)
+    hipLaunchKernelGGL((attn_decode_joint_k<true, false, long>), dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, p, n_slots);
+  else
+    hipLaunchKernelGGL(attn_decode_joint_k<true>, dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, p);
+  return owlk::check_launch(n_slots > 0 ? "attn_decode_joint_ring_slots_fwd" : "attn_decode_joint_ring_fwd");
+}
+
+extern "C" int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                               long skb, const void* vbuf, long ldv, long svb, void* o0, long ldo0,
+                                               void* o1, long ldo1, float* lse, long B, int H, int n0, int n1,
+                                               int head_dim, float scale, float score_bound, const long* state,
+                                               long window_tokens, long cap, void* stream) {
+  return attn_decode_joint_ring_launch(q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o0, ldo0, o1, ldo1, lse, B, H, n0,
+                                       n1, head_dim, scale, score_bound, state, window_tokens, cap, stream);
+}
+
+// Slot form for many audio + video sessions in one batch (sampling/stream_pool.py AVStreamPool; the reference's
+// inference/causvid_pipeline.py:112-163 serves one session per pipeline, on the mmattn.py:46-86 cache branch):
+// owlk_attn_decode_joint_ring_fwd with one state row {start, cached, offset, live} per slot, batch row b on row
+// b mod n_slots (the CFG halves [cond | uncond] of a session share one).  A live slot's o0, o1 and lse are the
+// single-state kernel's on that slot's rows and state, its key count its own; an idle slot reads nothing and gets
+// zero rows and lse -inf; a live slot outside the contract gets NaN rows, nothing read.
+extern "C" int owlk_attn_decode_joint_ring_slots_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                                     long skb, const void* vbuf, long ldv, long svb, void* o0,
+                                                     long ldo0, void* o1, long ldo1, float* lse, long B, int H, int n0,
+                                                     int n1, int head_dim, float scale, float score_bound,
+                                                     const long* state, long n_slots, long window_tokens, long cap,
+                                                     void* stream) {
+  OWLK_REQUIRE(lse && n_slots > 0 && B > 0 && B % n_slots == 0 && B <= 65535,
+               "attn_decode_joint_ring_slots_fwd: lse required, B=%ld batch rows a multiple of n_slots=%ld", B,
+               n_slots);
+  return attn_decode_joint_ring_launch(q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o0, ldo0, o1, ldo1, lse, B, H, n0,
+                                       n1, head_dim, scale, score_bound, state, window_tokens, cap, stream, n_slots);
 }
 
 // The DiT's own form of the five-tile ring decode, for streaming the dit-backbone audio + video core (the
@@ -1514,11 +1575,11 @@ extern "C" int owlk_attn_decode_joint_ring_fwd(const void* q, long ldq, long sqb
 // head_dim 64.  attn_decode_joint_k's ring body with one output o [B, Lq, H D] (row stride ldo, batch stride
 // sob): the same bits as owlk_attn_decode_joint_ring_fwd's o0 | o1 and lse on the same buffers and state.
 // Contract: 0 <= start < cap, cached >= 0, cached + Lnew <= cap; outside it NaN o rows and lse, nothing read.
-extern "C" int owlk_attn_decode_wide_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
-                                              long skb, const void* vbuf, long ldv, long svb, void* o, long ldo,
-                                              long sob, float* lse, long B, int H, long Lq, int head_dim, float scale,
-                                              float score_bound, const long* state, long Lnew, long window_tokens,
-                                              long cap, void* stream) {
+static int attn_decode_wide_ring_launch(const void* q, long ldq, long sqb, const void* kbuf, long ldk, long skb,
+                                        const void* vbuf, long ldv, long svb, void* o, long ldo, long sob, float* lse,
+                                        long B, int H, long Lq, int head_dim, float scale, float score_bound,
+                                        const long* state, long Lnew, long window_tokens, long cap, void* stream,
+                                        long n_slots = 0) {
   OWLK_REQUIRE(head_dim == 64, "attn_decode_wide_ring_fwd: head_dim %d not built (64)", head_dim);
   OWLK_REQUIRE(B > 0 && H > 0 && B <= 65535 && H <= 65535 && Lnew > 0 && state && window_tokens >= 0,
                "attn_decode_wide_ring_fwd: bad sizes");
@@ -1540,7 +1601,37 @@ extern "C" int owlk_attn_decode_wide_ring_fwd(const void* q, long ldq, long sqb,
   p.ldq = ldq; p.sqb = sqb; p.ldk = ldk; p.skb = skb; p.ldv = ldv; p.svb = svb; p.ldo0 = ldo; p.ldo1 = 0;
   p.Lq = Lq; p.Lkv = 0; p.n0 = (int)Lq; p.n1 = 0; p.H = H;  // Lkv from the device state
   p.scale_log2 = scale * LOG2E;
-  hipLaunchKernelGGL((attn_decode_joint_k<true, true>), dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0,
-                     (hipStream_t)stream, p);
-  return owlk::check_launch("attn_decode_wide_ring_fwd");
+  if (n_slots > 0)  // one state row per slot (owlk_attn_decode_wide_ring_slots_fwd)
+    hipLaunchKernelGGL((attn_decode_joint_k<true, true, long>), dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, p, n_slots);
+  else
+    hipLaunchKernelGGL((attn_decode_joint_k<true, true>), dim3(1, (unsigned)H, (unsigned)B), dim3(256), 0,
+                       (hipStream_t)stream, p);
+  return owlk::check_launch(n_slots > 0 ? "attn_decode_wide_ring_slots_fwd" : "attn_decode_wide_ring_fwd");
+}
+
+extern "C" int owlk_attn_decode_wide_ring_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                              long skb, const void* vbuf, long ldv, long svb, void* o, long ldo,
+                                              long sob, float* lse, long B, int H, long Lq, int head_dim, float scale,
+                                              float score_bound, const long* state, long Lnew, long window_tokens,
+                                              long cap, void* stream) {
+  return attn_decode_wide_ring_launch(q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o, ldo, sob, lse, B, H, Lq,
+                                      head_dim, scale, score_bound, state, Lnew, window_tokens, cap, stream);
+}
+
+// Slot form for many audio + video sessions of the dit backbone in one batch (sampling/stream_pool.py
+// AVDiTStreamPool; the reference's inference/causvid_pipeline.py:112-163 per session, a 65-row joint frame
+// through the attn.py:86-107 cache branch): owlk_attn_decode_wide_ring_fwd with one state row {start, cached,
+// offset, live} per slot, batch row b on row b mod n_slots.  Live, idle and out-of-contract slots as
+// owlk_attn_decode_joint_ring_slots_fwd; o and lse equal that entry's o0 | o1 and lse on the same buffers.
+extern "C" int owlk_attn_decode_wide_ring_slots_fwd(const void* q, long ldq, long sqb, const void* kbuf, long ldk,
+                                                    long skb, const void* vbuf, long ldv, long svb, void* o, long ldo,
+                                                    long sob, float* lse, long B, int H, long Lq, int head_dim,
+                                                    float scale, float score_bound, const long* state, long n_slots,
+                                                    long Lnew, long window_tokens, long cap, void* stream) {
+  OWLK_REQUIRE(lse && n_slots > 0 && B > 0 && B % n_slots == 0 && B <= 65535,
+               "attn_decode_wide_ring_slots_fwd: lse required, B=%ld batch rows a multiple of n_slots=%ld", B,
+               n_slots);
+  return attn_decode_wide_ring_launch(q, ldq, sqb, kbuf, ldk, skb, vbuf, ldv, svb, o, ldo, sob, lse, B, H, Lq,
+                                      head_dim, scale, score_bound, state, Lnew, window_tokens, cap, stream, n_slots);
 }

@@ -537,12 +537,16 @@ __global__ __launch_bounds__(256) void rope_rebase_k(bf16* __restrict__ kbuf, lo
 // from the device state {start, cached tokens, rope offset}: table row offset + t, token t's k / v at
 // row (start + cached + t) mod cap (each token wraps on its own: a 65-row frame straddles the end).
 // Outside the contract (qk_rope_kv_k's guard) q rows become NaN, cache and table are not touched.
-template <int D, bool RING>
+// SLOTS... (owlk_mm_qk_rope_fwd_kv_ring_slots, one trailing long n_slots): state is [n_slots, 4] rows {start,
+// cached, offset, live} and batch bb follows row bb mod n_slots, as in qk_rope_kv_k's slot form; an idle row gets
+// zero q rows and touches neither cache nor table, a live one runs the ring statements on its own row.
+template <int D, bool RING, typename... SLOTS>
 DEV void mm_qk_rope_kv_body(const bf16* __restrict__ qkv0, long ld0, const bf16* __restrict__ qkv1, long ld1, long B,
                             long nf, int n0, int n1, int H, const float* __restrict__ cosb,
                             const float* __restrict__ sinb, long ld_tab, long tab_off, bf16* __restrict__ qo,
                             long ldqo, long sqo, bf16* __restrict__ ko, long ldko, long sko, bf16* __restrict__ vo,
-                            long ldvo, long svo, const long* __restrict__ state, long n_tab, long cap) {
+                            long ldvo, long svo, const long* __restrict__ state, long n_tab, long cap,
+                            SLOTS... n_slots) {
   constexpr int CPR = D / 8;
   const long gid = (long)blockIdx.x * 256 + threadIdx.x;
   const long rowid = gid / CPR;  // (token, which, head)
@@ -552,6 +556,25 @@ DEV void mm_qk_rope_kv_body(const bf16* __restrict__ qkv0, long ld0, const bf16*
   const long tok = rowid / (3 * H);
   const int wh = rowid % (3 * H);  // which * H + head
   const long bb = tok / L, t = tok - bb * L;
+  [[maybe_unused]] long slot[4];  // the slot form's state row, alive for the whole body
+  if constexpr (sizeof...(SLOTS) > 0) {
+    static_assert(RING, "the slot form is a ring form");
+    // the slot's row in one 32-byte load, read from registers from here on; the host bounds B by 2^31
+    typedef long row_t __attribute__((ext_vector_type(4)));
+    const row_t row = *(const row_t*)(state + ((unsigned)bb % (unsigned)(n_slots, ...)) * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) slot[e] = row[e];
+    state = slot;
+    if (state[3] == 0) {  // idle slot: zero q rows, nothing else read or written
+      if (wh < H) {
+        const bf16x4 z4 = {(bf16)0.f, (bf16)0.f, (bf16)0.f, (bf16)0.f};
+        bf16* o = qo + bb * sqo + t * ldqo + (long)wh * D;
+        *(bf16x4*)(o + j * 4) = z4;
+        *(bf16x4*)(o + D / 2 + j * 4) = z4;
+      }
+      return;
+    }
+  }
   if constexpr (RING) {
     const long start = state[0], cached = state[1], off = state[2];
     if (start < 0 || start >= cap || cached < 0 || cached + L > cap || off < 0 || off + L > n_tab) {
@@ -610,7 +633,7 @@ __global__ __launch_bounds__(256) void mm_qk_rope_kv_k(const bf16* __restrict__ 
                                ldko, sko, vo, ldvo, svo, nullptr, 0, 0);
 }
 
-template <int D>
+template <int D, typename... SLOTS>
 __global__ __launch_bounds__(256) void mm_qk_rope_kv_ring_k(const bf16* __restrict__ qkv0, long ld0,
                                                             const bf16* __restrict__ qkv1, long ld1, long B, long nf,
                                                             int n0, int n1, int H, const float* __restrict__ cosb,
@@ -618,9 +641,10 @@ __global__ __launch_bounds__(256) void mm_qk_rope_kv_ring_k(const bf16* __restri
                                                             bf16* __restrict__ qo, long ldqo, long sqo,
                                                             bf16* __restrict__ kbuf, long ldk, long skb,
                                                             bf16* __restrict__ vbuf, long ldv, long svb,
-                                                            const long* __restrict__ state, long n_tab, long cap) {
+                                                            const long* __restrict__ state, long n_tab, long cap,
+                                                            SLOTS... n_slots) {
   mm_qk_rope_kv_body<D, true>(qkv0, ld0, qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, 0, qo, ldqo, sqo, kbuf, ldk,
-                              skb, vbuf, ldv, svb, state, n_tab, cap);
+                              skb, vbuf, ldv, svb, state, n_tab, cap, n_slots...);
 }
 
 // backward: d(q_rot) -> inverse rotation -> rms_norm backward (recomputing xhat from raw qkv)
@@ -1302,11 +1326,11 @@ extern "C" int owlk_mm_qk_rope_fwd_kv(const void* qkv0, long ld0, const void* qk
 // (start + cached + t) mod cap of the ring buffers kbuf / vbuf [B, cap, H D].  Contract: 0 <= start < cap,
 // cached >= 0, cached + L <= cap, 0 <= offset, offset + L <= n_tab (L = nf (n0 + n1)); outside it NaN q rows,
 // cache and table untouched.
-extern "C" int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf,
-                                           int n0, int n1, int H, int D, const float* cosb, const float* sinb,
-                                           long ld_tab, long n_tab, const long* state, void* qo, long ldqo, long sqo,
-                                           void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
-                                           void* stream) {
+static int mm_qk_rope_kv_ring_launch(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf, int n0,
+                                     int n1, int H, int D, const float* cosb, const float* sinb, long ld_tab,
+                                     long n_tab, const long* state, void* qo, long ldqo, long sqo, void* kbuf,
+                                     long ldk, long skb, void* vbuf, long ldv, long svb, long cap, void* stream,
+                                     long n_slots = 0) {
   OWLK_REQUIRE(D == 64 || D == 128, "mm_qk_rope_fwd_kv_ring: head_dim %d unsupported", D);
   OWLK_REQUIRE(B > 0 && nf > 0 && n0 > 0 && n1 > 0 && H > 0,
                "mm_qk_rope_fwd_kv_ring: bad sizes B=%ld nf=%ld n0=%d n1=%d", B, nf, n0, n1);
@@ -1326,7 +1350,15 @@ extern "C" int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const voi
   const long threads = B * L * 3 * H * (D / 8);
   OWLK_REQUIRE(threads < (1L << 31) * 256, "mm_qk_rope_fwd_kv_ring: too many rows for one launch");
   dim3 g((unsigned)((threads + 255) / 256));
-  if (D == 64)
+  if (n_slots > 0 && D == 64)  // one state row per slot (owlk_mm_qk_rope_fwd_kv_ring_slots)
+    hipLaunchKernelGGL((mm_qk_rope_kv_ring_k<64, long>), g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
+                       (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, (bf16*)qo, ldqo, sqo,
+                       (bf16*)kbuf, ldk, skb, (bf16*)vbuf, ldv, svb, state, n_tab, cap, n_slots);
+  else if (n_slots > 0)
+    hipLaunchKernelGGL((mm_qk_rope_kv_ring_k<128, long>), g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0,
+                       ld0, (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, (bf16*)qo, ldqo, sqo,
+                       (bf16*)kbuf, ldk, skb, (bf16*)vbuf, ldv, svb, state, n_tab, cap, n_slots);
+  else if (D == 64)
     hipLaunchKernelGGL(mm_qk_rope_kv_ring_k<64>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
                        (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, (bf16*)qo, ldqo, sqo,
                        (bf16*)kbuf, ldk, skb, (bf16*)vbuf, ldv, svb, state, n_tab, cap);
@@ -1334,7 +1366,33 @@ extern "C" int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const voi
     hipLaunchKernelGGL(mm_qk_rope_kv_ring_k<128>, g, dim3(256), 0, (hipStream_t)stream, (const bf16*)qkv0, ld0,
                        (const bf16*)qkv1, ld1, B, nf, n0, n1, H, cosb, sinb, ld_tab, (bf16*)qo, ldqo, sqo,
                        (bf16*)kbuf, ldk, skb, (bf16*)vbuf, ldv, svb, state, n_tab, cap);
-  return owlk::check_launch("mm_qk_rope_fwd_kv_ring");
+  return owlk::check_launch(n_slots > 0 ? "mm_qk_rope_fwd_kv_ring_slots" : "mm_qk_rope_fwd_kv_ring");
+}
+
+extern "C" int owlk_mm_qk_rope_fwd_kv_ring(const void* qkv0, long ld0, const void* qkv1, long ld1, long B, long nf,
+                                           int n0, int n1, int H, int D, const float* cosb, const float* sinb,
+                                           long ld_tab, long n_tab, const long* state, void* qo, long ldqo, long sqo,
+                                           void* kbuf, long ldk, long skb, void* vbuf, long ldv, long svb, long cap,
+                                           void* stream) {
+  return mm_qk_rope_kv_ring_launch(qkv0, ld0, qkv1, ld1, B, nf, n0, n1, H, D, cosb, sinb, ld_tab, n_tab, state, qo,
+                                   ldqo, sqo, kbuf, ldk, skb, vbuf, ldv, svb, cap, stream);
+}
+
+// Slot form for many audio + video sessions in one batch (sampling/stream_pool.py AVStreamPool; the reference's
+// inference/causvid_pipeline.py:112-163 serves one session per pipeline, on the mmattn.py:46-86 cache branch):
+// owlk_mm_qk_rope_fwd_kv_ring with one state row {start, cached, offset, live} per slot, batch row b on row
+// b mod n_slots (the CFG halves [cond | uncond] of a session share one).  A live slot's rows are the
+// single-state kernel's; an idle one gets zero q rows; one outside the contract NaN q rows; neither touches
+// the cache or the table, and no slot's state reaches another's rows.
+extern "C" int owlk_mm_qk_rope_fwd_kv_ring_slots(const void* qkv0, long ld0, const void* qkv1, long ld1, long B,
+                                                 long nf, int n0, int n1, int H, int D, const float* cosb,
+                                                 const float* sinb, long ld_tab, long n_tab, const long* state,
+                                                 long n_slots, void* qo, long ldqo, long sqo, void* kbuf, long ldk,
+                                                 long skb, void* vbuf, long ldv, long svb, long cap, void* stream) {
+  OWLK_REQUIRE(n_slots > 0 && B > 0 && B < (1L << 31) && B % n_slots == 0,
+               "mm_qk_rope_fwd_kv_ring_slots: B=%ld batch rows must be a multiple of n_slots=%ld", B, n_slots);
+  return mm_qk_rope_kv_ring_launch(qkv0, ld0, qkv1, ld1, B, nf, n0, n1, H, D, cosb, sinb, ld_tab, n_tab, state, qo,
+                                   ldqo, sqo, kbuf, ldk, skb, vbuf, ldv, svb, cap, stream, n_slots);
 }
 
 extern "C" int owlk_qk_rope_bwd(const void* dqk, long ldd, const void* qkv, long ldq, long T, int H, int D,

@@ -46,6 +46,12 @@ _SIGS = {
     "owlk_mm_qk_rope_fwd_kv_ring": [P, L, P, L, L, L, I, I, I, I, P, P, L, L, P, P, L, L, P, L, L, P, L, L, L, P],
     "owlk_attn_decode_joint_ring_fwd": [P, L, L, P, L, L, P, L, L, P, L, P, L, P, L, I, I, I, I, F, F, P, L, L, P],
     "owlk_attn_decode_wide_ring_fwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, L, I, L, I, F, F, P, L, L, L, P],
+    "owlk_mm_qk_rope_fwd_kv_ring_slots": [P, L, P, L, L, L, I, I, I, I, P, P, L, L, P, L, P, L, L, P, L, L, P, L, L, L,
+                                          P],
+    "owlk_attn_decode_joint_ring_slots_fwd": [P, L, L, P, L, L, P, L, L, P, L, P, L, P, L, I, I, I, I, F, F, P, L, L,
+                                              L, P],
+    "owlk_attn_decode_wide_ring_slots_fwd": [P, L, L, P, L, L, P, L, L, P, L, L, P, L, I, L, I, F, F, P, L, L, L, L,
+                                             P],
     "owlk_qk_rope_bwd": [P, L, P, L, L, I, I, P, P, L, L, L, L, P, P, L, P],
     "owlk_qk_rope_bwd_ws_bytes": [L, I, I],
     "owlk_qk_rope_bwd_bias": [P, L, P, L, L, I, I, P, P, L, L, L, L, P, P, L, P, P, L, P],

@@ -576,6 +576,72 @@ def attn_decode_wide_ring_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0,
     return o, lse
 
 
+def mm_qk_rope_fwd_kv_ring_slots(qkv0, qkv1, B, nf, n0, n1, H, D, cos, sin, state, q_out, kbuf, vbuf):
+    """mm_qk_rope_fwd_kv_ring with one state row per slot (state [n_slots, 4] {start, cached, offset, live},
+    batch row b on row b mod n_slots): a live slot's rows as the single-state kernel writes them, an idle
+    slot's q rows zero and its cache rows untouched, a slot outside the contract NaN q rows."""
+    L = nf * (n0 + n1)
+    n_slots = _slot_state(state, B)
+    for t, rows, nm in ((qkv0, B * nf * n0, "qkv0"), (qkv1, B * nf * n1, "qkv1")):
+        assert t.dim() == 2 and t.shape == (rows, 3 * H * D) and t.stride(1) == 1 and t.dtype == BF16, nm
+    assert q_out.shape == (B, L, H * D) and q_out.stride(2) == 1 and q_out.dtype == BF16, "q_out"
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    assert cos.stride(1) == 1 and sin.stride(0) == cos.stride(0) and cos.shape[1] * 2 == D
+    call("owlk_mm_qk_rope_fwd_kv_ring_slots", ptr(qkv0), qkv0.stride(0), ptr(qkv1), qkv1.stride(0), B, nf, n0, n1, H,
+         D, ptr(cos), ptr(sin), cos.stride(0), cos.shape[0], ptr(state), n_slots, ptr(q_out), q_out.stride(1),
+         q_out.stride(0), ptr(kbuf), kbuf.stride(1), kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0),
+         kbuf.shape[1], stream())
+
+
+def attn_decode_joint_ring_slots_fwd(q, kbuf, vbuf, H, D, n0, n1, state, window_tokens=0, scale=None,
+                                     score_bound=0.0, o0=None, o1=None):
+    """attn_decode_joint_ring_fwd with one state row per slot (see mm_qk_rope_fwd_kv_ring_slots), each slot
+    with its own key count: a live slot's o0, o1 and lse are the single-state kernel's, an idle slot's rows
+    zero and lse -inf with nothing read -> (o0, o1, lse)."""
+    _v3(q, "q")
+    B, Lq = q.shape[0], q.shape[1]
+    assert decode_joint_supported(D, n0, n1) and Lq == n0 + n1, \
+        f"attn_decode_joint_ring_slots_fwd: head_dim {D} / frame of {n0} + {n1} rows not supported"
+    assert q.shape[2] >= H * D
+    n_slots = _slot_state(state, B)
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    if o0 is None:
+        o0 = torch.empty(B * n0, H * D, device=q.device, dtype=BF16)
+    if o1 is None:
+        o1 = torch.empty(B * n1, H * D, device=q.device, dtype=BF16)
+    _rowmajor(o0, "o0"), _rowmajor(o1, "o1")
+    assert o0.shape == (B * n0, H * D) and o1.shape == (B * n1, H * D)
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32)
+    call("owlk_attn_decode_joint_ring_slots_fwd", ptr(q), q.stride(1), q.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), ptr(o0), o0.stride(0), ptr(o1), o1.stride(0),
+         ptr(lse), B, H, n0, n1, D, float(scale if scale is not None else D ** -0.5), float(score_bound), ptr(state),
+         n_slots, int(window_tokens), kbuf.shape[1], stream())
+    return o0, o1, lse
+
+
+def attn_decode_wide_ring_slots_fwd(q, kbuf, vbuf, H, D, state, Lnew, window_tokens=0, scale=None, score_bound=0.0,
+                                    o=None):
+    """attn_decode_wide_ring_fwd with one state row per slot (see mm_qk_rope_fwd_kv_ring_slots): a live slot's
+    o and lse are the single-state kernel's, an idle slot's o rows zero and lse -inf with nothing read.  The
+    bits of attn_decode_joint_ring_slots_fwd's o0 | o1 and lse."""
+    _v3(q, "q")
+    B, Lq = q.shape[0], q.shape[1]
+    assert D == 64 and 0 < Lq <= WIDE_DECODE_ROWS, \
+        f"attn_decode_wide_ring_slots_fwd: head_dim {D} / {Lq} query rows not supported"
+    assert q.shape[2] >= H * D
+    n_slots = _slot_state(state, B)
+    _ring_state(state, kbuf, vbuf, B, H, D)
+    if o is None:
+        o = torch.empty(B, Lq, H * D, device=q.device, dtype=BF16)
+    assert o.shape == (B, Lq, H * D) and o.stride(2) == 1 and o.dtype == BF16 and o.device == q.device, "o"
+    lse = torch.empty(B, H, Lq, device=q.device, dtype=F32)
+    call("owlk_attn_decode_wide_ring_slots_fwd", ptr(q), q.stride(1), q.stride(0), ptr(kbuf), kbuf.stride(1),
+         kbuf.stride(0), ptr(vbuf), vbuf.stride(1), vbuf.stride(0), ptr(o), o.stride(1), o.stride(0), ptr(lse), B, H,
+         Lq, D, float(scale if scale is not None else D ** -0.5), float(score_bound), ptr(state), n_slots, int(Lnew),
+         int(window_tokens), kbuf.shape[1], stream())
+    return o, lse
+
+
 def qk_rope_bwd(dqk, qkv, rstd, H, D, cos, sin, dqkv, tab_off=0, tpos_div=0, dbias=None):
     """-> dqkv[:, :2HD]; with dbias (fp32 [2HD]) also dbias += column sums of those outputs (the q / k
     part of the qkv bias gradient), fused into the same pass where the shape allows."""

@@ -125,7 +125,7 @@ class Attn(nn.Module):
         # whatever the slots' offsets (an idle pool has none)
         slots = getattr(kv_cache, "n_slots", None) is not None
         ring = (offset > 0 or slots) and getattr(kv_cache, "ring", False)
-        wide = ring and not slots and K.decode_wide_supported(D, L)
+        wide = ring and K.decode_wide_supported(D, L)
         if ring and (block_mask is not None or kv_cache.dev is None or
                      not (wide or K.decode_dev_supported(D, L))):
             raise RuntimeError("a RingKVCache decodes one frame at a time on the device-state path "
@@ -139,8 +139,9 @@ class Attn(nn.Module):
             # frame, head_dim 64) takes the five-tile wide attention
             rope_kv, attend = (K.qk_rope_fwd_kv_ring, K.attn_decode_wide_ring_fwd if wide else
                                K.attn_decode_ring_fwd) if ring else (K.qk_rope_fwd_kv_dev, K.attn_decode_fwd)
-            if slots:
-                rope_kv, attend = K.qk_rope_fwd_kv_ring_slots, K.attn_decode_ring_slots_fwd
+            if slots:  # the wide slot form for the audio + video pool's 65- to 80-row frame (AVDiTStreamPool)
+                rope_kv, attend = K.qk_rope_fwd_kv_ring_slots, (K.attn_decode_wide_ring_slots_fwd if wide else
+                                                                K.attn_decode_ring_slots_fwd)
             kb, vb = kv_cache.bufs[self.layer_idx]
             q = torch.empty(B, L, d, device=qkv.device, dtype=torch.bfloat16)
             rope_kv(qkv, B, L, H, D, self.rope.cos, self.rope.sin, kv_cache.dev, q, kb, vb)

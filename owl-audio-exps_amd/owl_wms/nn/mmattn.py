@@ -285,7 +285,9 @@ class MMDiTBlock(nn.Module):
     def forward(self, x0, x1, cond0, cond1, block_mask=None, kv_cache=None):
         if kv_cache is not None:
             with torch.no_grad():
-                if getattr(kv_cache, "ring", False) and kv_cache.get_offset(self.attn.layer_idx) > 0:
+                # a SlotRingKVCache (sampling/stream_pool.py AVStreamPool) decodes whatever its slots' offsets
+                if getattr(kv_cache, "ring", False) and (kv_cache.get_offset(self.attn.layer_idx) > 0 or
+                                                         getattr(kv_cache, "n_slots", None) is not None):
                     return self._forward_ring_decode(x0, x1, cond0, cond1, block_mask, kv_cache)
                 if self.decoding and self._decode_ok(block_mask, kv_cache):
                     return self._forward_decode(x0, x1, cond0, cond1, block_mask, kv_cache)
@@ -409,7 +411,9 @@ class MMDiTBlock(nn.Module):
         depends on a host position and a captured step stays valid across frames, wraps and rebases.
         The new rows are roped at the ABSOLUTE offset (the vector's third word), not at the cached length
         _forward_cached / _forward_decode use as mmattn.py:60-62 does: after an eviction the cached length
-        points at positions live keys already hold."""
+        points at positions live keys already hold.
+        A SlotRingKVCache (sampling/stream_pool.py AVStreamPool) takes the two kernels' slot forms: one state
+        row {start, cached, offset, live} per session, batch row b on row b mod n_slots."""
         a = self.attn
         d, H, D, n0, n1, B, nf, T = self._cached_dims(x0)
         if nf != 1 or D != 64 or kv_cache.dev is None or kv_cache.noise_caches != 0.0 or \
@@ -422,11 +426,14 @@ class MMDiTBlock(nn.Module):
         li = a.layer_idx
         kb, vb = kv_cache.bufs[li]
         q = torch.empty(B, T, d, device=x0.device, dtype=BF16)
-        K.mm_qk_rope_fwd_kv_ring(qkv[0], qkv[1], B, nf, n0, n1, H, D, a.rope.cos, a.rope.sin, kv_cache.dev, q, kb, vb)
+        slots = getattr(kv_cache, "n_slots", None) is not None
+        rope_kv, attend = (K.mm_qk_rope_fwd_kv_ring_slots, K.attn_decode_joint_ring_slots_fwd) if slots else \
+            (K.mm_qk_rope_fwd_kv_ring, K.attn_decode_joint_ring_fwd)
+        rope_kv(qkv[0], qkv[1], B, nf, n0, n1, H, D, a.rope.cos, a.rope.sin, kv_cache.dev, q, kb, vb)
         del qkv
         window = block_mask.window if block_mask is not None else None
-        os_ = K.attn_decode_joint_ring_fwd(q, kb, vb, H, D, n0, n1, kv_cache.dev, int(window) * T if window else 0,
-                                           score_bound=K.qk_norm_bound(D))[:2]
+        os_ = attend(q, kb, vb, H, D, n0, n1, kv_cache.dev, int(window) * T if window else 0,
+                     score_bound=K.qk_norm_bound(D))[:2]
         if kv_cache.should_update:
             kv_cache.commit_device(li, T)
         return self._cached_tail(os_, xs, ms, B)
